@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the interval-join hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR] [--full]
 
 Metric (BASELINE.json): emitted overlap-pairs/s (+ achieved HBM GB/s) of pb.overlap on the
 100M x 5M, 24-contig synthetic set (SURVEY.md section 8d generator), inputs resident in HBM
@@ -18,17 +18,26 @@ all-gatherv inside the timed region ("scaling": "strong": total work is fixed as
 torch.distributed.run (one rank per GPU, 127.0.0.1 rendezvous); under an external launcher the ranks are used
 as given and `n_gpus` must equal --gpus.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+A plain run sets up, warms up, times the K steps, writes the last step's outputs (--dump-outputs DIR) and prints ONE JSON
+line on rank 0 (contract in the task statement) with
   roofline      -- dominant kernel: algorithmic bytes PER LAUNCH / live HIP-event time of a launch vs 8 TB/s (a kernel
-                   that runs several times per step processes that fraction of the step's bytes each time); `traffic` =
-                   HBM bytes per launch of that kernel from two rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE) that
+                   that runs several times per step processes that fraction of the step's bytes each time).
+Everything that takes runs of its own comes with --full only (null in the line of a plain run):
+  roofline.traffic -- HBM bytes per launch of that kernel from two rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE) that
                    this run makes over itself (N=1; null when rocprofv3 is unavailable or --no-pmc)
   cpu_baseline  -- the oracle's CPU port timed on the host cores (N=1 only): all cores on the IDENTICAL input (index built
                    with all cores, busy cores reported), 1 thread on a 2 M-row sample; one pass per probe row.
-and, for overlap: `two_pass_ms_per_step` (the count -> scan -> fill pair a call of unknown capacity runs, i.e. what
-ivj_overlap and the front door's pb.overlap take) and
-`host_path_s` (numpy columns in pageable host memory -> pb.overlap's C entry point -> numpy pairs, PCIe inclusive);
-for all three operations `stream_path_s` (the same columns through the streaming session, batch by batch).
+  for overlap: `two_pass_ms_per_step` (the count -> scan -> fill pair a call of unknown capacity runs, i.e. what
+  ivj_overlap and the front door's pb.overlap take) and
+  `host_path_s` (numpy columns in pageable host memory -> pb.overlap's C entry point -> numpy pairs, PCIe inclusive);
+  for all three operations `stream_path_s` (the same columns through the streaming session, batch by batch);
+  N > 1: `phases_ms` (the same steps once more without the exchange).
+
+--dump-outputs DIR: what the last timed step computed, as a caller of the timed path receives it, in DIR/<name>.npy
+(float64, exact for the int32 / int64 results).  Pair and piece lists are put in a canonical order first (sorted by their
+first two columns: the fused join's order of probe rows is not fixed); outputs longer than DUMP_ROWS rows keep a fixed,
+seeded sample of DUMP_ROWS rows.  The inputs are seeded as well, so two builds run with the same arguments can be compared
+file by file.
 """
 import argparse
 import csv
@@ -97,7 +106,15 @@ def parse():
                          "wavefront's probes by position could buy (VERDICT r5 item 1a)")
     ap.add_argument("--force-dist", action="store_true",
                     help="take the multi-process code path (RCCL init, sharding, all-gatherv) even with one rank")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: PMC traffic passes, CPU baseline, two-pass / host / stream paths, "
+                         "N > 1 join-only steps (--no-pmc / --no-cpu-baseline / --no-extras leave parts out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float64; canonical order, seeded sample of long outputs)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 WORKLOADS = {
@@ -172,6 +189,37 @@ def algorithmic_bytes(op, n_p, n_b, n_out):
     if op == "merge":
         return 12 * n_b + 20 * n_out                       # read the frame, write (contig, start, end, n_intervals)
     return 8 * n_p + 8 * n_b + 12 * n_p + contig      # nearest k=1
+
+
+DUMP_ROWS = 1_000_000       # rows kept of a longer output: at most 4 columns x 8 B x 1 M rows = 32 MB per dump
+DUMP_SEED = 20260101
+OUTPUT_NAMES = {"overlap": ("probe_idx", "build_idx"), "count_overlaps": ("count",), "coverage": ("coverage",),
+                "nearest": ("build_idx", "distance", "n_found"), "subtract": ("row", "start", "end"),
+                "merge": ("contig", "start", "end", "n_intervals")}
+CANONICAL_ORDER = ("overlap", "subtract", "merge")      # lists whose row order the kernels do not fix: sorted by (column 0, column 1)
+
+
+def dump_outputs(out_dir, op, result):
+    """--dump-outputs: one step's result tensors (on any device) -> out_dir/<name>.npy, float64.  Returns the rows of the full output."""
+    import torch
+    cols = [t.reshape(-1) for t in (result if isinstance(result, (tuple, list)) else (result,))]
+    names = OUTPUT_NAMES[op]
+    assert len(cols) == len(names), (op, len(cols))
+    n = int(cols[0].numel())
+    order = None
+    if op in CANONICAL_ORDER and n:
+        key = cols[0].to(torch.int64) * (1 << 32) + (cols[1].to(torch.int64) + (1 << 31))     # column 0 >= 0, column 1 any int32
+        order = torch.sort(key, stable=True).indices
+        del key
+    if n > DUMP_ROWS:
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_ROWS, replace=False))
+        pos = torch.from_numpy(pick).to(cols[0].device)
+        order = pos if order is None else order[pos]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, c in zip(names, cols):
+        v = c if order is None else c[order]
+        np.save(os.path.join(out_dir, name + ".npy"), v.cpu().numpy().astype(np.float64))
+    return n
 
 
 def cgroup_cpu_quota():
@@ -629,6 +677,12 @@ def main():
             f"; closing barrier {(t0 + elapsed - t_host[-1]) * 1e3:.3f}")
     ktimes = join.engine.timings()
     join.engine.enable_timing(0)
+    if args.dump_outputs and rank == 0:
+        # before anything else runs a step: the --full legs below write into the same result buffers
+        t_d = time.perf_counter()
+        n_rows = dump_outputs(args.dump_outputs, op, out)
+        log(f"[bench] outputs of the last timed step ({n_rows:,} rows, at most {DUMP_ROWS:,} kept) -> {args.dump_outputs} "
+            f"in {time.perf_counter() - t_d:.1f}s")
 
     t = torch.tensor([local_units], dtype=torch.int64)
     tmax = torch.tensor([elapsed], dtype=torch.float64)
@@ -648,7 +702,7 @@ def main():
     # N > 1: the same steps once more WITHOUT the exchange (what --no-gather would report), so that the line always carries
     # the join-only rate next to the headline and the exchange's exposed share of the step
     join_only_ms = None
-    if gather:
+    if gather and args.full:
         state["no_gather"] = True
         kj = max(1, min(args.steps, 5))
         step()
@@ -674,7 +728,7 @@ def main():
     traffic, traffic_detail = None, None
     if args.pmc_inner:
         return                                   # the run rocprofv3 wraps ends here: no extras, no line
-    if rank == 0 and n_gpus == 1 and not args.no_pmc and dom_name:
+    if rank == 0 and n_gpus == 1 and args.full and not args.no_pmc and dom_name:
         if in_profiler():
             traffic_detail = {"skipped": "already running under a profiler"}
         else:
@@ -720,7 +774,7 @@ def main():
 
     # overlap: the deterministic count -> scan -> fill pair (what a cold call with unknown capacity runs) ...
     two_pass_ms = None
-    if op == "overlap" and not args.no_extras and not args.two_pass:
+    if op == "overlap" and args.full and not args.no_extras and not args.two_pass:
         k2 = max(1, min(args.steps, 5))
         join.overlap(d_probe, d_build, True, nc, out=state.get("out"), fused=False, partition_mode=args.partition_mode)
         barrier()
@@ -734,7 +788,7 @@ def main():
         two_pass_ms = float(tp.item()) / k2 * 1e3
     # ... and the PCIe-inclusive host-buffer path (numpy in pageable memory -> ivj_overlap -> numpy pairs)
     host_path = None
-    if op == "overlap" and not args.no_extras and rank == 0 and n_gpus == 1:
+    if op == "overlap" and args.full and not args.no_extras and rank == 0 and n_gpus == 1:
         try:
             best = None
             for _ in range(2):
@@ -750,7 +804,7 @@ def main():
     # ... and the streaming session on the same host columns (ivj_stream_*: H2D of batch i+1 || join of batch i || D2H of
     # batch i-1, results consumed as zero-copy views of the pinned slots): first submit -> last delivered result
     stream_path = None
-    if op in ("overlap", "nearest", "count_overlaps") and not args.no_extras and rank == 0 and n_gpus == 1:
+    if op in ("overlap", "nearest", "count_overlaps") and args.full and not args.no_extras and rank == 0 and n_gpus == 1:
         try:
             from polars_bio_amd import _engine as E
             code = {"overlap": E.STREAM_OVERLAP, "nearest": E.STREAM_NEAREST, "count_overlaps": E.STREAM_COUNT}[op]
@@ -777,7 +831,7 @@ def main():
             stream_path = {"error": repr(e)}
 
     cpu = None
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline and op in ("overlap", "nearest", "count_overlaps"):
+    if rank == 0 and n_gpus == 1 and args.full and not args.no_cpu_baseline and op in ("overlap", "nearest", "count_overlaps"):
         try:
             cpu = cpu_baseline(op, probe, build, nc, args.cpu_sample)
         except Exception as e:  # the baseline must never take the bench line down

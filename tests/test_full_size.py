@@ -249,7 +249,7 @@ def test_bench_gpus_2_on_whatever_devices_there_are():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--scale", "0.03", "--steps", "2", "--warmup", "1",
-                          "--no-pmc", "--no-cpu-baseline", "--no-extras"], capture_output=True, text=True, env=env, timeout=900)
+                          "--full", "--no-pmc", "--no-cpu-baseline", "--no-extras"], capture_output=True, text=True, env=env, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(line) == 1

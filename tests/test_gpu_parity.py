@@ -343,7 +343,7 @@ def test_bench_contract_and_rccl_path_single_rank(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29541", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1")
     for extra in ([], ["--force-dist"]):
-        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--scale", "0.02", "--steps", "2",
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--scale", "0.02", "--steps", "2",
                               "--warmup", "1", "--cpu-sample", "200000"] + extra,
                              capture_output=True, text=True, env=env, timeout=600)
         assert out.returncode == 0, out.stderr[-2000:]
@@ -359,6 +359,39 @@ def test_bench_contract_and_rccl_path_single_rank(tmp_path):
             assert "all-gatherv" in j["config"]["parallelism"]
         else:
             assert j["cpu_baseline"]["kind"] == "port" and j["cpu_baseline"]["value"] > 0
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_timed_outputs(tmp_path):
+    """bench.py without --full times its steps and nothing else (no CPU baseline, PMC traffic or extra paths in the line);
+    --dump-outputs writes the pairs of the last timed step as float64 in canonical order: the oracle's pair set."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        env.pop(k, None)
+    out_dir = tmp_path / "outputs"
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--scale", "0.02", "--steps", "3", "--warmup", "1",
+                          "--dump-outputs", str(out_dir)], capture_output=True, text=True, env=env, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["value"] > 0
+    assert j["cpu_baseline"] is None and j["two_pass_ms_per_step"] is None and j["host_path"] is None and j["stream_path"] is None
+    assert j["roofline"]["traffic"] is None
+    files = sorted(os.listdir(out_dir))
+    assert files == ["build_idx.npy", "probe_idx.npy"]
+    assert sum(os.path.getsize(out_dir / f) for f in files) <= 64 << 20
+    p, b = np.load(out_dir / "probe_idx.npy"), np.load(out_dir / "build_idx.npy")
+    assert p.dtype == np.float64 and b.dtype == np.float64
+    assert len(p) == j["config"]["units_per_step"] < 1_000_000        # small enough to be dumped whole
+    import bench
+    probe, build, nc, _ = bench.gen_workload("overlap_100M_5M_24contig", 0.02)
+    ep, eb = O.overlap_fast(O.Index(O.Side(*build), nc), O.Side(*probe), True)
+    o = np.lexsort((eb, ep))
+    assert (p == ep[o]).all() and (b == eb[o]).all()
 
 
 def test_fused_single_pass_matches_two_pass(eng):

@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 tag=$1; shift
-B="python bench.py"
+B="python bench.py --full"
 for stage in "$@"; do
   o=gpurun_out/${tag}_${stage//[^A-Za-z0-9_=-]/_}
   case "$stage" in

@@ -8,7 +8,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 tag=$1; shift
-B="python bench.py"
+B="python bench.py --full"
 Q="--no-pmc --no-cpu-baseline --no-extras --kernel-table"
 run_stage() {
   local stage=$1 sfx=$2
