@@ -327,6 +327,26 @@ int ivj_merge_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_opts* opts, int64_t min
                   int32_t* contig_dev, int32_t* start_dev, int32_t* end_dev, int64_t* n_intervals_dev, int64_t* n_merged);
 int ivj_coverage_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, const ivj_opts* opts, int64_t* coverage_dev);
 
+/* ---- group ids: joins keyed on extra columns (on_cols) --------------------------------------------------------------------------
+ * Every kernel partitions by one int32 id per row and ignores ids outside [0, n_contigs).  A dense GROUP id over (chrom, on_col
+ * values...) passed as `contig`, with n_contigs = the number of groups, makes every operation of this header run within groups.
+ * Input per side: the chrom id column plus n_cols (<= 8) int32 code columns, one per on_col, from dictionaries shared by the two
+ * sides (codes of column j in [0, cards[j]); a negative code is a null).  key = ((chrom * cards[0] + code_0) * cards[1] + code_1) ...
+ * in [0, D), D = n_contigs * prod(cards); D > 2^31 is refused with IVJ_EINVAL (the message names the cardinalities).
+ * Numbering rule: gid = rank of the row's key among the keys present in the BUILD side, in ascending key order; -1 for a row with a
+ * null / out-of-range component or a key the build side lacks.  *n_groups = G, the number of present keys.  group_keys (optional,
+ * NULL: not written): row g = (chrom, code_0, ..., code_{n_cols-1}) of gid g, G x (1 + n_cols) int32 row-major; keys_cap rows are
+ * available, IVJ_ECAPACITY (with *n_groups set, the gids complete) when G exceeds it -- min(n_build, D) rows always suffice.
+ * With dictionaries sorted the way the caller sorts chrom, gids ascend in (chrom, on values) order.
+ * A gid column may alias its side's contig column.  For merge / cluster of one frame pass it as the build side (n_probe = 0). */
+/* device pointers for the columns; probe_codes / build_codes are HOST arrays of n_cols device pointers, cards a host array.
+ * Passes: mark (one bit per build key; the bitmap privatized in LDS up to 2^18 keys, else a test before the global atomic OR),
+ * rank (popcount + exclusive scan of the D / 32 words), remap of both sides, group table.  Blocks until *n_groups is known.
+ * Scratch: 12 bytes per 32 keys of D from the context's arena. */
+int ivj_group_ids_dev(ivj_ctx* ctx, const int32_t* probe_contig, const int32_t* const* probe_codes, int64_t n_probe,
+                      const int32_t* build_contig, const int32_t* const* build_codes, int64_t n_build, int32_t n_cols, const int32_t* cards,
+                      int32_t n_contigs, int32_t* probe_gid, int32_t* build_gid, int32_t* group_keys, int64_t keys_cap, int32_t* n_groups);
+
 /* Arrow C Data Interface IMPORT of one side (zero copy): `array` / `schema` describe a struct array (or record
  * batch) whose children named contig / start / end (any order, other children ignored) are int32 without nulls --
  * what the reference hands its executor as an ArrowArrayStream batch after the chrom column has been dictionary
@@ -566,6 +586,11 @@ int ivj_host_shard(const int32_t* contig, const int32_t* start, const int32_t* e
                    int64_t* counts, int32_t* const* out_contig, int32_t* const* out_start, int32_t* const* out_end, int32_t* const* out_row, int32_t threads);
 /* rows per contig (the weights of the LPT contig -> rank assignment): hist[n_contigs] */
 int ivj_host_contig_hist(const int32_t* contig, int64_t n, int32_t n_contigs, int64_t* hist, int32_t threads);
+/* ivj_group_ids_dev on host columns (threaded; no device, no context): the same numbering rule, bit for bit.  The front door
+ * composes group ids here, where the chrom ids already are: no extra bytes cross to the device. */
+int ivj_host_group_ids(const int32_t* probe_contig, const int32_t* const* probe_codes, int64_t n_probe, const int32_t* build_contig,
+                       const int32_t* const* build_codes, int64_t n_build, int32_t n_cols, const int32_t* cards, int32_t n_contigs,
+                       int32_t* probe_gid, int32_t* build_gid, int32_t* group_keys, int64_t keys_cap, int32_t* n_groups, int32_t threads);
 
 /* int32 -> int64: key columns materialised in HBM back to the dtype of the caller's frame. */
 int ivj_host_widen_i32(const int32_t* src, int64_t n, int64_t* dst, int32_t threads);

@@ -424,6 +424,83 @@ static int ivj_host_contig_hist_impl(const int32_t* contig, int64_t n, int32_t n
     return IVJ_OK;
 }
 
+// the key of row i (group.hip.h: group_key), -1 for a null / out-of-range component
+static inline int64_t host_group_key(const GroupCols& c, int64_t i) {
+    const int32_t ch = c.contig[i];
+    if ((uint32_t)ch >= (uint32_t)c.n_contigs) return -1;
+    uint32_t key = (uint32_t)ch;
+    for (int j = 0; j < c.k; ++j) {
+        const int32_t v = c.code[j][i];
+        if ((uint32_t)v >= (uint32_t)c.card[j]) return -1;
+        key = key * (uint32_t)c.card[j] + (uint32_t)v;
+    }
+    return (int64_t)key;
+}
+
+// host twin of ivj_group_ids_dev: the same numbering rule over host columns (mark with a test before the atomic OR, a serial
+// popcount scan over the D / 32 words, threaded remap of both sides, the group table from the set bits)
+static int ivj_host_group_ids_impl(const int32_t* probe_contig, const int32_t* const* probe_codes, int64_t n_probe, const int32_t* build_contig,
+                                   const int32_t* const* build_codes, int64_t n_build, int32_t n_cols, const int32_t* cards, int32_t n_contigs,
+                                   int32_t* probe_gid, int32_t* build_gid, int32_t* group_keys, int64_t keys_cap, int32_t* n_groups, int32_t threads) {
+    if (!n_groups) return fail(IVJ_EINVAL, "group ids: n_groups is NULL");
+    int64_t D = 0;
+    IVJ_TRY(group_domain(n_contigs, n_cols, cards, &D));
+    GroupCols pc, bc;
+    IVJ_TRY(group_cols(&pc, probe_contig, probe_codes, n_probe, n_cols, cards, n_contigs, "probe"));
+    IVJ_TRY(group_cols(&bc, build_contig, build_codes, n_build, n_cols, cards, n_contigs, "build"));
+    if ((n_probe > 0 && !probe_gid) || (n_build > 0 && !build_gid)) return fail(IVJ_EINVAL, "group ids: a gid output is NULL");
+    if (keys_cap < 0 || (keys_cap > 0 && !group_keys)) return fail(IVJ_EINVAL, "group ids: bad group_keys / keys_cap");
+    *n_groups = 0;
+    const int64_t words = (D + 31) / 32;
+    std::vector<uint32_t> bitmap(n_build > 0 ? (size_t)words : 0, 0u), rank(bitmap.size(), 0u);
+    if (!bitmap.empty()) {
+        fd_parallel(n_build, fd_threads(n_build, threads, 1 << 16), [&](int, int64_t lo, int64_t hi) {
+            for (int64_t i = lo; i < hi; ++i) {
+                const int64_t key = host_group_key(bc, i);
+                if (key < 0) continue;
+                const uint32_t m = 1u << (key & 31);
+                uint32_t* w = &bitmap[(size_t)(key >> 5)];
+                if (!(__atomic_load_n(w, __ATOMIC_RELAXED) & m)) __atomic_fetch_or(w, m, __ATOMIC_RELAXED);
+            }
+        });
+    }
+    uint32_t G = 0;
+    for (size_t w = 0; w < bitmap.size(); ++w) { rank[w] = G; G += (uint32_t)__builtin_popcount(bitmap[w]); }
+    auto remap = [&](const GroupCols& c, int32_t* gid) {
+        if (c.n == 0) return;
+        fd_parallel(c.n, fd_threads(c.n, threads, 1 << 16), [&](int, int64_t lo, int64_t hi) {
+            for (int64_t i = lo; i < hi; ++i) {
+                const int64_t key = bitmap.empty() ? -1 : host_group_key(c, i);
+                int32_t g = -1;
+                if (key >= 0) {
+                    const uint32_t word = bitmap[(size_t)(key >> 5)], m = 1u << (key & 31);
+                    if (word & m) g = (int32_t)(rank[(size_t)(key >> 5)] + (uint32_t)__builtin_popcount(word & (m - 1u)));
+                }
+                gid[i] = g;
+            }
+        });
+    };
+    remap(pc, probe_gid);
+    remap(bc, build_gid);
+    if (group_keys && keys_cap > 0) {
+        const int stride = 1 + n_cols;
+        for (size_t w = 0; w < bitmap.size(); ++w) {
+            uint32_t bits = bitmap[w];
+            int64_t g = rank[w];
+            for (; bits && g < keys_cap; bits &= bits - 1u, ++g) {
+                uint32_t rem = (uint32_t)(w * 32 + (size_t)__builtin_ctz(bits));
+                int32_t* row = group_keys + g * stride;
+                for (int j = n_cols - 1; j >= 0; --j) { row[1 + j] = (int32_t)(rem % (uint32_t)cards[j]); rem /= (uint32_t)cards[j]; }
+                row[0] = (int32_t)rem;
+            }
+        }
+    }
+    *n_groups = (int32_t)G;
+    if (group_keys && (int64_t)G > keys_cap)
+        return fail(IVJ_ECAPACITY, "group ids: " + std::to_string(G) + " groups, group_keys holds " + std::to_string(keys_cap) + " rows");
+    return IVJ_OK;
+}
+
 
 // no C++ exception may cross the C ABI (std::thread / std::vector can throw under resource exhaustion)
 #define IVJ_HOST_GUARD(call)                                                                        \
@@ -462,6 +539,12 @@ int ivj_host_shard(const int32_t* contig, const int32_t* start, const int32_t* e
 }
 int ivj_host_contig_hist(const int32_t* contig, int64_t n, int32_t n_contigs, int64_t* hist, int32_t threads) {
     IVJ_HOST_GUARD(ivj_host_contig_hist_impl(contig, n, n_contigs, hist, threads))
+}
+int ivj_host_group_ids(const int32_t* probe_contig, const int32_t* const* probe_codes, int64_t n_probe, const int32_t* build_contig,
+                       const int32_t* const* build_codes, int64_t n_build, int32_t n_cols, const int32_t* cards, int32_t n_contigs,
+                       int32_t* probe_gid, int32_t* build_gid, int32_t* group_keys, int64_t keys_cap, int32_t* n_groups, int32_t threads) {
+    IVJ_HOST_GUARD(ivj_host_group_ids_impl(probe_contig, probe_codes, n_probe, build_contig, build_codes, n_build, n_cols, cards, n_contigs,
+                                           probe_gid, build_gid, group_keys, keys_cap, n_groups, threads))
 }
 #undef IVJ_HOST_GUARD
 

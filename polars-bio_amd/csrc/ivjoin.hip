@@ -28,6 +28,7 @@
 #include "onesweep.hip.h"
 #include "ixsort3.hip.h"
 #include "scan.hip.h"
+#include "group.hip.h"
 
 using namespace ivj;
 
@@ -40,6 +41,7 @@ using namespace ivj;
 #include "host_sortscan.hip.h"
 #include "host_stream.hip.h"
 #include "host_comm.hip.h"
+#include "host_group.hip.h"
 
 // =============================================================================== C ABI
 

@@ -494,3 +494,99 @@ def from_arrow(t: pa.Table, output_type: str, zero_based: bool):
         ctx = datafusion.SessionContext()
         return ctx.from_arrow(t) if hasattr(ctx, "from_arrow") else ctx.from_arrow_table(t)
     raise ValueError("Only polars.LazyFrame, polars.DataFrame and pandas.DataFrame are supported")
+
+
+# ---- on_cols: extra join keys (include/ivjoin.h "group ids") ----------------------------------------------------------
+
+MAX_GROUP_KEYS = 1 << 31          # D = n_contigs * prod(cardinalities) the group-id entries accept
+
+
+def _is_stringish(t: pa.DataType) -> bool:
+    return (pa.types.is_string(t) or pa.types.is_large_string(t)
+            or (hasattr(pa.types, "is_string_view") and pa.types.is_string_view(t)))
+
+
+def on_col_type(name: str, *types) -> pa.DataType:
+    """The one type the values of on_col ``name`` are compared in across the frames: strings (any string type, or a
+    dictionary / categorical of strings) as large_string, integers (or dictionaries of integers) as int64, any other type only
+    when every frame has exactly it.  ValueError when the frames' types cannot be unified."""
+    vt = [t.value_type if pa.types.is_dictionary(t) else t for t in types]
+    if all(_is_stringish(t) or pa.types.is_null(t) for t in vt):
+        return pa.large_string()
+    if all(pa.types.is_integer(t) or pa.types.is_null(t) for t in vt):
+        return pa.int64()
+    if all(t == vt[0] for t in vt):
+        return vt[0]
+    raise ValueError(f"on_cols column '{name}' has types that cannot be joined: {', '.join(str(t) for t in types)}")
+
+
+def _as_on_type(col, typ: pa.DataType):
+    if pa.types.is_dictionary(col.type):
+        col = pc.cast(col, col.type.value_type)
+    return col if col.type == typ else pc.cast(col, typ)
+
+
+def on_col_dictionary(cols, typ: pa.DataType) -> pa.Array:
+    """Sorted distinct non-null values of the given columns (cast to ``typ``): codes then ascend in value order, so that group ids
+    ascend in (chrom, on values) order as chrom ids do in ``encode_frame``."""
+    parts = []
+    for c in cols:
+        c = _as_on_type(c, typ)
+        u = pc.unique(c.combine_chunks() if isinstance(c, pa.ChunkedArray) else c)
+        parts.append(u.combine_chunks() if isinstance(u, pa.ChunkedArray) else u)
+    u = pc.drop_null(pc.unique(pa.concat_arrays(parts))) if parts else pa.array([], typ)
+    u = u.combine_chunks() if isinstance(u, pa.ChunkedArray) else u
+    return pc.take(u, pc.sort_indices(u))
+
+
+def on_col_codes(col, dictionary: pa.Array, typ: pa.DataType) -> np.ndarray:
+    """Per-row codes of one on_col in ``dictionary`` (int32; -1: null, or a value the dictionary lacks)."""
+    if len(col) == 0:
+        return np.empty(0, np.int32)
+    c = _as_on_type(col, typ)
+    idx = pc.fill_null(pc.index_in(c, value_set=dictionary), -1)
+    idx = idx.combine_chunks() if isinstance(idx, pa.ChunkedArray) else idx
+    return idx.to_numpy(zero_copy_only=False).astype(np.int32, copy=False)
+
+
+def encode_on_cols(tables, on_cols):
+    """-> (per table: list of code arrays, cardinalities, dictionaries, types): one sorted dictionary per on_col shared by all
+    the given tables (both frames of a join, the one frame of merge)."""
+    codes = [[] for _ in tables]
+    cards, dicts, types = [], [], []
+    for name in on_cols:
+        typ = on_col_type(name, *[t.schema.field(name).type for t in tables])
+        d = on_col_dictionary([t.column(name) for t in tables], typ)
+        for k, t in enumerate(tables):
+            codes[k].append(on_col_codes(t.column(name), d, typ))
+        cards.append(len(d))
+        dicts.append(d)
+        types.append(typ)
+    return codes, cards, dicts, types
+
+
+def check_group_domain(n_contigs: int, cards, on_cols) -> None:
+    d = int(n_contigs)
+    for c in cards:
+        d *= int(c)
+    if d > MAX_GROUP_KEYS:
+        desc = ", ".join(f"'{n}': {c}" for n, c in zip(on_cols, cards))
+        raise ValueError(f"on_cols key space too large: {n_contigs} contigs x ({desc}) distinct values = {d} keys, the limit is 2^31")
+
+
+def group_sides(probe, build, n_contigs: int, probe_codes, build_codes, cards, on_cols):
+    """(contig, start, end) of both sides + the on_col codes -> the same sides with GROUP ids as contig, the number of groups
+    and the group table (chrom id, code_1, ..., code_K) per group id (ivj_host_group_ids)."""
+    check_group_domain(n_contigs, cards, on_cols)
+    pg, bg, g, table = H.group_ids(probe[0], probe_codes, build[0], build_codes, cards, n_contigs)
+    return (pg, probe[1], probe[2]), (bg, build[1], build[2]), g, table
+
+
+def cast_on_values(values: pa.Array, typ: pa.DataType) -> pa.Array:
+    """on_col values taken out of its dictionary back to the frame's column type where that cast exists."""
+    if values.type == typ:
+        return values
+    try:
+        return pc.cast(values, typ)
+    except (pa.ArrowInvalid, pa.ArrowNotImplementedError, pa.ArrowTypeError):
+        return pc.cast(values, pa.string()) if pa.types.is_large_string(values.type) else values

@@ -40,7 +40,7 @@ ABI_SYMBOLS = [
     "ivj_overlap_arrow_stream", "ivj_count_overlaps_arrow_stream", "ivj_nearest_arrow_stream", "ivj_arrow_encode_keys", "ivj_arrow_keys_free",
     "ivj_overlap_arrow_stream_lazy", "ivj_count_overlaps_arrow_stream_lazy", "ivj_nearest_arrow_stream_lazy",
     "ivj_arrow_take_stream",
-    "ivj_host_shard", "ivj_host_contig_hist",
+    "ivj_host_shard", "ivj_host_contig_hist", "ivj_group_ids_dev", "ivj_host_group_ids",
     "ivj_host_narrow_i32", "ivj_host_encode_utf8", "ivj_host_encode_keys64", "ivj_host_remap_i32", "ivj_host_take", "ivj_host_scatter", "ivj_host_widen_i32",
 ]
 
@@ -221,6 +221,10 @@ def load_library() -> C.CDLL:
         L.ivj_host_widen_i32.argtypes = [vp, C.c_int64, vp, C.c_int32]
         L.ivj_host_shard.argtypes = [vp, vp, vp, C.c_int64, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.c_int32]
         L.ivj_host_contig_hist.argtypes = [vp, C.c_int64, C.c_int32, vp, C.c_int32]
+        L.ivj_group_ids_dev.argtypes = [vp, vp, C.POINTER(vp), C.c_int64, vp, C.POINTER(vp), C.c_int64, C.c_int32, vp, C.c_int32, vp, vp, vp,
+                                        C.c_int64, C.POINTER(C.c_int32)]
+        L.ivj_host_group_ids.argtypes = [vp, C.POINTER(vp), C.c_int64, vp, C.POINTER(vp), C.c_int64, C.c_int32, vp, C.c_int32, vp, vp, vp,
+                                         C.c_int64, C.POINTER(C.c_int32), C.c_int32]
         names3 = C.POINTER(C.c_char_p)
         L.ivj_overlap_arrow_stream.argtypes = [vp, vp, vp, names3, names3, O, C.c_char_p, C.c_char_p, C.c_int64, C.c_int64, vp]
         L.ivj_count_overlaps_arrow_stream.argtypes = [vp, vp, vp, names3, names3, O, C.c_char_p, C.c_int64, C.c_int64, vp]
@@ -705,6 +709,21 @@ class Engine:
         """ivj_take_dev: Arrow take of one 4- or 8-byte device column; negative indices -> 0 / null bit."""
         _check(self.L, self.L.ivj_take_dev(self.h, C.c_void_p(src_ptr), int(elem_bytes), C.c_void_p(idx_ptr), int(n),
                                             C.c_void_p(dst_ptr), C.c_void_p(validity_ptr or None)), "ivj_take_dev")
+
+    def group_ids_dev(self, probe_contig_ptr: int, probe_code_ptrs, n_probe: int, build_contig_ptr: int, build_code_ptrs, n_build: int,
+                      cards, n_contigs: int, probe_gid_ptr: int, build_gid_ptr: int, keys_ptr: int, keys_cap: int) -> int:
+        """ivj_group_ids_dev (device pointers; the code pointer lists and ``cards`` are host values) -> number of groups."""
+        k = len(cards)
+        cards_a = (C.c_int32 * max(k, 1))(*[int(c) for c in cards])
+        pc = (C.c_void_p * max(k, 1))(*[C.c_void_p(int(p)) for p in probe_code_ptrs])
+        bc = (C.c_void_p * max(k, 1))(*[C.c_void_p(int(p)) for p in build_code_ptrs])
+        g = C.c_int32(0)
+        _check(self.L, self.L.ivj_group_ids_dev(self.h, C.c_void_p(probe_contig_ptr or None), C.cast(pc, C.POINTER(C.c_void_p)), int(n_probe),
+                                                 C.c_void_p(build_contig_ptr or None), C.cast(bc, C.POINTER(C.c_void_p)), int(n_build), k,
+                                                 C.cast(cards_a, C.c_void_p), int(n_contigs), C.c_void_p(probe_gid_ptr or None),
+                                                 C.c_void_p(build_gid_ptr or None), C.c_void_p(keys_ptr or None), int(keys_cap), C.byref(g)),
+               "ivj_group_ids_dev")
+        return g.value
 
     def cluster_dev(self, ix: DeviceIndex, opts: _Opts, min_dist: int, cluster_ptr: int, start_ptr: int, end_ptr: int) -> int:
         n = C.c_int64(0)

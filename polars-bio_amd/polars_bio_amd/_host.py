@@ -123,3 +123,33 @@ def shard_by_owner(side, owner: np.ndarray, world: int):
     _check(L, L.ivj_host_shard(_ptr(c), _ptr(s), _ptr(e), n, _ptr(owner), nc, int(world), _ptr(counts), arrs[0], arrs[1], arrs[2], arrs[3], THREADS),
            "ivj_host_shard")
     return [((outs[0][r], outs[1][r], outs[2][r]), outs[3][r]) for r in range(world)]
+
+
+def group_ids(probe_contig: np.ndarray, probe_codes, build_contig: np.ndarray, build_codes, cards, n_contigs: int):
+    """ivj_host_group_ids: (probe gids, build gids, n_groups, group table (n_groups, 1 + K) int32) -- the rank of every row's
+    (chrom, code_1, ..., code_K) key among the keys of the build side, -1 for a null component or a key the build side lacks."""
+    L = load_library()
+    k = len(cards)
+    pcont = np.ascontiguousarray(probe_contig, np.int32)
+    bcont = np.ascontiguousarray(build_contig, np.int32)
+    pcodes = [np.ascontiguousarray(c, np.int32) for c in probe_codes]
+    bcodes = [np.ascontiguousarray(c, np.int32) for c in build_codes]
+    assert len(pcodes) == k and len(bcodes) == k
+    assert all(len(c) == len(pcont) for c in pcodes) and all(len(c) == len(bcont) for c in bcodes)
+    cards_a = np.ascontiguousarray(cards, np.int32).reshape(-1)
+    if cards_a.size == 0:
+        cards_a = np.zeros(1, np.int32)
+    domain = int(n_contigs)
+    for c in cards:
+        domain *= int(c)
+    cap = max(1, min(len(bcont), domain))
+    keys = np.empty((cap, 1 + k), np.int32)
+    pg = np.empty(len(pcont), np.int32)
+    bg = np.empty(len(bcont), np.int32)
+    parr = (C.c_void_p * max(k, 1))(*[c.ctypes.data for c in pcodes])
+    barr = (C.c_void_p * max(k, 1))(*[c.ctypes.data for c in bcodes])
+    g = C.c_int32(0)
+    _check(L, L.ivj_host_group_ids(_ptr(pcont), C.cast(parr, C.POINTER(C.c_void_p)), len(pcont), _ptr(bcont), C.cast(barr, C.POINTER(C.c_void_p)),
+                                   len(bcont), k, _ptr(cards_a), int(n_contigs), _ptr(pg), _ptr(bg), _ptr(keys), cap, C.byref(g), THREADS),
+           "ivj_host_group_ids")
+    return pg, bg, g.value, keys[:g.value].copy()

@@ -151,17 +151,47 @@ def _ids(ch, u) -> np.ndarray:
     return out
 
 
-def encode_probe_batch(rb: pa.RecordBatch, cols1, dictionary):
+def encode_probe_batch(rb: pa.RecordBatch, cols1, dictionary, groups=None):
+    """One probe batch -> (contig, start, end) int32; with ``groups`` (a BuildGroups) contig holds group ids."""
     for c in cols1:
         if c not in rb.schema.names:
             raise ValueError(f"column '{c}' not found in {rb.schema.names}")
     t = pa.Table.from_batches([rb])
     ids = _ids(t.column(cols1[0]), dictionary)
+    if groups is not None:
+        ids = groups.probe_ids(t, ids)
     return ids, A._coord_to_i32(t.column(cols1[1]), cols1[1]), A._coord_to_i32(t.column(cols1[2]), cols1[2])
 
 
+class BuildGroups:
+    """on_cols of a streaming session: the build side fixes the on_col dictionaries and the group table once; every probe batch is
+    mapped against the table (ivj_host_group_ids with the table's G rows as the build side: the same keys, so the same ranks)."""
+
+    def __init__(self, t2: pa.Table, build, n_contigs: int, on_cols):
+        for c in on_cols:
+            assert c in t2.column_names, f"on_cols ['{c}'] not found in {t2.column_names}"
+        self.on_cols, self.n_contigs = list(on_cols), int(n_contigs)
+        self.types = [A.on_col_type(c, t2.schema.field(c).type) for c in on_cols]
+        self.dicts = [A.on_col_dictionary([t2.column(c)], typ) for c, typ in zip(on_cols, self.types)]
+        self.cards = [len(d) for d in self.dicts]
+        codes = [A.on_col_codes(t2.column(c), d, typ) for c, d, typ in zip(on_cols, self.dicts, self.types)]
+        empty = (np.empty(0, np.int32),) * 3
+        _, self.build, self.n_groups, self.table = A.group_sides(empty, build, n_contigs, [np.empty(0, np.int32)] * len(on_cols), codes,
+                                                                 self.cards, on_cols)
+
+    def probe_ids(self, t: pa.Table, chrom_ids: np.ndarray) -> np.ndarray:
+        codes = []
+        for c, d, typ in zip(self.on_cols, self.dicts, self.types):
+            assert c in t.column_names, f"on_cols ['{c}'] not found in {t.column_names}"
+            A.on_col_type(c, t.schema.field(c).type, typ)          # ValueError for a batch type that cannot be compared
+            codes.append(A.on_col_codes(t.column(c), d, typ))
+        tab = self.table
+        g, _, _, _ = A.H.group_ids(chrom_ids, codes, tab[:, 0], [tab[:, 1 + j] for j in range(len(codes))], self.cards, self.n_contigs)
+        return g
+
+
 def range_batches(engine, op: str, df1, df2, cols1, cols2, zero_based: bool, assemble, batch_rows: int = 8_000_000,
-                  limit: Optional[int] = None, k: int = 1, include_overlaps: bool = True) -> Iterator[pa.Table]:
+                  limit: Optional[int] = None, k: int = 1, include_overlaps: bool = True, on_cols=None) -> Iterator[pa.Table]:
     """Generator of result tables, one per probe batch (in probe order).  ``assemble(batch_table, t2, result_dict)``
     builds the output rows of one batch; ``limit`` bounds the total number of rows and stops the input early."""
     assert op in OPS
@@ -169,6 +199,10 @@ def range_batches(engine, op: str, df1, df2, cols1, cols2, zero_based: bool, ass
     code = {"overlap": STREAM_OVERLAP, "count_overlaps": STREAM_COUNT, "nearest": STREAM_NEAREST}[op]
     t2 = A.to_arrow(df2)
     build, n_contigs, dictionary = encode_build(t2, cols2)
+    groups = None
+    if on_cols:
+        groups = BuildGroups(t2, build, n_contigs, on_cols)
+        build, n_contigs = groups.build, max(groups.n_groups, 1)
     left = None if limit is None else int(limit)
     if left is not None and left <= 0:
         return
@@ -193,7 +227,7 @@ def range_batches(engine, op: str, df1, df2, cols1, cols2, zero_based: bool, ass
         for rb in iter_record_batches(df1, batch_rows):
             pending[n_sub] = pa.Table.from_batches([rb])
             n_sub += 1
-            res = stream.submit(encode_probe_batch(rb, cols1, dictionary))
+            res = stream.submit(encode_probe_batch(rb, cols1, dictionary, groups))
             if res is not None:
                 yield deliver(res)
                 if left is not None and left <= 0:

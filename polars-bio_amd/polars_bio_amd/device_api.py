@@ -45,6 +45,36 @@ class DeviceJoin:
         self.engine = Engine(device)
         self.engine.set_stream(torch.cuda.current_stream(device).cuda_stream)
 
+    def group(self, probe: DeviceSide, build: DeviceSide, probe_codes, build_codes, cards, n_contigs: int):
+        """Joins keyed on extra columns (on_cols) in HBM: ivj_group_ids_dev turns (contig, code_1, ..., code_K) of both sides into
+        dense group ids.  ``probe_codes`` / ``build_codes``: one contiguous int32 CUDA tensor per on_col (codes of a dictionary
+        shared by both sides, in [0, cards[j]); negative = null).  -> (probe', build', n_groups, group_keys) where the sides
+        carry the group ids as ``contig`` (-1: a null component or a key the build side lacks), so every other method of this
+        class, called with ``n_contigs=max(n_groups, 1)``, runs within groups; group_keys is an (n_groups, 1 + K) int32 tensor
+        of (contig, code_1, ..., code_K) per group id, in ascending key order."""
+        torch = self.torch
+        cards = [int(c) for c in cards]
+        if len(probe_codes) != len(cards) or len(build_codes) != len(cards):
+            raise ValueError("one code column per on_col on each side")
+        for side, codes in ((probe, probe_codes), (build, build_codes)):
+            for t in codes:
+                if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or int(t.shape[0]) != side.n:
+                    raise ValueError("code columns must be contiguous int32 CUDA tensors of the side's length")
+        domain = int(n_contigs)
+        for c in cards:
+            domain *= c
+        if domain > (1 << 31):
+            raise ValueError(f"on_cols key space too large: {n_contigs} contigs x {cards} distinct values = {domain} keys, the limit is 2^31")
+        dev = build.start.device
+        cap = max(1, min(build.n, domain))
+        keys = torch.empty((cap, 1 + len(cards)), dtype=torch.int32, device=dev)
+        pg = torch.empty(probe.n, dtype=torch.int32, device=probe.start.device)
+        bg = torch.empty(build.n, dtype=torch.int32, device=dev)
+        g = self.engine.group_ids_dev(probe.contig.data_ptr(), [t.data_ptr() for t in probe_codes], probe.n, build.contig.data_ptr(),
+                                      [t.data_ptr() for t in build_codes], build.n, cards, int(n_contigs), pg.data_ptr(), bg.data_ptr(),
+                                      keys.data_ptr(), cap)
+        return (DeviceSide(pg, probe.start, probe.end, probe.row_id), DeviceSide(bg, build.start, build.end, build.row_id), g, keys[:g])
+
     def build_index(self, build: DeviceSide, strict: bool, n_contigs: int, with_end_order: bool = False):
         return self.engine.index_build_dev(build.as_c(), make_opts(strict, n_contigs), with_end_order)
 

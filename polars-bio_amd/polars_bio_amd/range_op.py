@@ -61,10 +61,42 @@ def _parse_overlap_output_mode(overlap_output: str) -> int:
 
 
 def _validate_overlap_input(col1, col2, on_cols, suffixes, output_type):
-    # reference: range_op_helpers.py:379-399
-    assert on_cols is None, "on_cols is not supported yet"
+    """reference: range_op_helpers.py:379-399.  -> on_cols as a list, or None for no extra join keys ([] is None)."""
     assert output_type in A.OUTPUT_TYPES, (
         "Only polars.LazyFrame, polars.DataFrame and pandas DataFrame are supported")
+    if on_cols is None:
+        return None
+    if isinstance(on_cols, str):
+        on_cols = [on_cols]
+    on_cols = list(on_cols)
+    if not on_cols:
+        return None
+    assert all(isinstance(c, str) for c in on_cols), "on_cols must be a list of column names"
+    assert len(set(on_cols)) == len(on_cols), "on_cols names a column twice"
+    interval = set(DEFAULT_INTERVAL_COLUMNS if col1 is None else col1) | set(DEFAULT_INTERVAL_COLUMNS if col2 is None else col2)
+    bad = [c for c in on_cols if c in interval]
+    assert not bad, f"on_cols may not name the interval columns: {bad}"
+    return on_cols
+
+
+def _schema_names(df):
+    from . import _streaming as S
+    sch = S.source_schema(df)
+    if sch is None:
+        return None
+    return list(sch.names)
+
+
+def _check_on_cols_present(on_cols, *frames):
+    """Every on_col must exist in every frame (AssertionError otherwise, as the reference's own checks fail)."""
+    if not on_cols:
+        return
+    for df in frames:
+        names = _schema_names(df)
+        if names is None:
+            continue                                          # a bare stream: checked when its first batch is encoded
+        missing = [c for c in on_cols if c not in names]
+        assert not missing, f"on_cols {missing} not found in {names}"
 
 
 def _low_memory_batch_rows() -> int:
@@ -111,6 +143,8 @@ def _overlap_join_rows(t1, t2, probe, build, n_contigs, keys, cols1, cols2, suff
     rows = eng.overlap_rows(probe, build, strict=zero_based, n_contigs=n_contigs, as_arrow=True)
     col = lambda name: rows.column(name).to_numpy(zero_copy_only=False)     # views of the library's buffers (owned by `rows`)
     p_idx, b_idx, contig = col("probe_idx"), col("build_idx"), col("contig")
+    if len(keys) > 5 and keys[5] is not None:
+        contig = A.H.take(keys[5], np.ascontiguousarray(contig, np.int32))  # on_cols: the ids are group ids -> chrom ids of the group table
     other1 = [n for n in t1.column_names if n not in c1]
     other2 = [n for n in t2.column_names if n not in c2]
     take = (lambda t, idx: A.take_rows_device(eng, t, idx)) if others_on_device else (lambda t, idx: A.take_rows(t, idx))
@@ -183,16 +217,19 @@ def _assemble_nearest(t1, t2, idx, dist, nf, suffixes, distance, keys=None) -> p
     return res
 
 
-def _assemble_count(t1, counts, naive_query, cols1, suffixes) -> pa.Table:
+def _assemble_count(t1, counts, naive_query, cols1, suffixes, on_cols=None) -> pa.Table:
     if naive_query:
         return t1.append_column("count", pa.array(counts, type=pa.int64()))
+    # the reference sweep's select list (range_op.py:583-592): suffixed key columns, the on_cols (df1's values), count
     res = pa.table({f"{c}{suffixes[0]}": t1.column(c) for c in cols1})
+    for c in on_cols or ():
+        res = res.append_column(c, t1.column(c))
     return res.append_column("count", pa.array(counts, type=pa.int64()))
 
 
 # ---- streaming / lazy front end ----------------------------------------------------
 
-def _stream(op, df1, df2, cols1, cols2, assemble, batch_rows, limit, k=1, include_overlaps=True, zero_based=None):
+def _stream(op, df1, df2, cols1, cols2, assemble, batch_rows, limit, k=1, include_overlaps=True, zero_based=None, on_cols=None):
     from . import _streaming as S
     if zero_based is None:
         zero_based = validate_coordinate_systems(df1, df2)
@@ -200,7 +237,7 @@ def _stream(op, df1, df2, cols1, cols2, assemble, batch_rows, limit, k=1, includ
     cols2 = list(DEFAULT_INTERVAL_COLUMNS if cols2 is None else cols2)
     rows = int(batch_rows) if batch_rows else _low_memory_batch_rows()
     return zero_based, S.range_batches(default_engine(), op, df1, df2, cols1, cols2, zero_based, assemble, batch_rows=rows, limit=limit,
-                                       k=k, include_overlaps=include_overlaps)
+                                       k=k, include_overlaps=include_overlaps, on_cols=on_cols)
 
 
 def _lazy_reader(df1, df2, zero_based, batches, assemble_empty):
@@ -224,16 +261,17 @@ def _lazy_reader(df1, df2, zero_based, batches, assemble_empty):
 
 
 def overlap_batches(df1, df2, suffixes=("_1", "_2"), cols1=None, cols2=None, batch_rows: int = 8_000_000, limit=None,
-                    overlap_output: str = "join", distinct_output: bool = False, as_reader: bool = False, _zero_based=None):
+                    overlap_output: str = "join", distinct_output: bool = False, as_reader: bool = False, _zero_based=None, on_cols=None):
     """Streaming form of ``overlap``: df2 is indexed once on the device, df1 is CONSUMED batch by batch -- an Arrow C stream
     producer (``__arrow_c_stream__`` / ``pyarrow.RecordBatchReader``), a Parquet / CSV / BED path, or an in-memory frame --
     and one pyarrow.Table of joined rows is yielded per probe batch (H2D, join and D2H of consecutive batches overlap).
     ``limit`` bounds the number of result rows and stops reading df1 early.  ``as_reader=True`` returns a
     pyarrow.RecordBatchReader instead of a generator.  Counterpart of the reference's lazy ``range_lazy_scan`` generator
-    (/root/reference/polars_bio/range_op_io.py:100-174) and ``range_operation_lazy`` (src/lib.rs:154-214)."""
+    (/root/reference/polars_bio/range_op_io.py:100-174) and ``range_operation_lazy`` (src/lib.rs:154-214).
+    ``on_cols``: extra join keys; df2 fixes their dictionaries, a df1 value df2 lacks matches nothing."""
     mode = _parse_overlap_output_mode(overlap_output)
     asm = lambda bt, t2, res: _assemble_overlap(bt, t2, res["probe_idx"], res["build_idx"], mode, distinct_output, suffixes)
-    zero_based, gen = _stream("overlap", df1, df2, cols1, cols2, asm, batch_rows, limit, zero_based=_zero_based)
+    zero_based, gen = _stream("overlap", df1, df2, cols1, cols2, asm, batch_rows, limit, zero_based=_zero_based, on_cols=on_cols)
     if as_reader:
         e = np.empty(0, np.int32)
         return _lazy_reader(df1, df2, zero_based, gen, lambda a, b: _assemble_overlap(a, b, e, e, mode, distinct_output, suffixes))
@@ -241,21 +279,22 @@ def overlap_batches(df1, df2, suffixes=("_1", "_2"), cols1=None, cols2=None, bat
 
 
 def count_overlaps_batches(df1, df2, suffixes=("", "_"), cols1=None, cols2=None, batch_rows: int = 8_000_000, limit=None,
-                           naive_query: bool = True, as_reader: bool = False, _zero_based=None):
+                           naive_query: bool = True, as_reader: bool = False, _zero_based=None, on_cols=None):
     """Streaming form of ``count_overlaps`` (see ``overlap_batches``): df1 rows + ``count`` per probe batch, df1 order kept."""
     c1 = list(DEFAULT_INTERVAL_COLUMNS if cols1 is None else cols1)
-    asm = lambda bt, t2, res: _assemble_count(bt, res["counts"], naive_query, c1, suffixes)
-    zero_based, gen = _stream("count_overlaps", df1, df2, cols1, cols2, asm, batch_rows, limit, zero_based=_zero_based)
+    asm = lambda bt, t2, res: _assemble_count(bt, res["counts"], naive_query, c1, suffixes, on_cols)
+    zero_based, gen = _stream("count_overlaps", df1, df2, cols1, cols2, asm, batch_rows, limit, zero_based=_zero_based, on_cols=on_cols)
     if as_reader:
-        return _lazy_reader(df1, df2, zero_based, gen, lambda a, b: _assemble_count(a, np.empty(0, np.int64), naive_query, c1, suffixes))
+        return _lazy_reader(df1, df2, zero_based, gen, lambda a, b: _assemble_count(a, np.empty(0, np.int64), naive_query, c1, suffixes, on_cols))
     return gen
 
 
 def nearest_batches(df1, df2, suffixes=("_1", "_2"), cols1=None, cols2=None, k: int = 1, overlap: bool = True, distance: bool = True,
-                    batch_rows: int = 8_000_000, limit=None, as_reader: bool = False, _zero_based=None):
+                    batch_rows: int = 8_000_000, limit=None, as_reader: bool = False, _zero_based=None, on_cols=None):
     """Streaming form of ``nearest`` (see ``overlap_batches``)."""
     asm = lambda bt, t2, res: _assemble_nearest(bt, t2, res["build_idx"], res["dist"], res["n_found"], suffixes, distance)
-    zero_based, gen = _stream("nearest", df1, df2, cols1, cols2, asm, batch_rows, limit, k=int(k), include_overlaps=bool(overlap), zero_based=_zero_based)
+    zero_based, gen = _stream("nearest", df1, df2, cols1, cols2, asm, batch_rows, limit, k=int(k), include_overlaps=bool(overlap), zero_based=_zero_based,
+                              on_cols=on_cols)
     if as_reader:
         kk = int(k)
         return _lazy_reader(df1, df2, zero_based, gen, lambda a, b: _assemble_nearest(a, b, np.empty((0, kk), np.int32), np.empty((0, kk), np.int64),
@@ -299,12 +338,24 @@ def _polars_lazy_result(df1, df2, zero_based, limit, batches_fn, **kw):
     return set_coordinate_system(PL.range_lazy_scan(make, schema), zero_based)
 
 
-def _prepare(df1, df2, cols1, cols2):
+def _prepare(df1, df2, cols1, cols2, on_cols=None):
+    """-> (t1, t2, probe, build, n_contigs, keys).  With on_cols the sides carry GROUP ids over (chrom, on values) as contig and
+    n_contigs is the number of groups (ivj_host_group_ids); keys keeps the per-row chrom ids (the result's chrom columns) and, as
+    a sixth item, the chrom id of every group id (None without on_cols)."""
     cols1 = list(DEFAULT_INTERVAL_COLUMNS if cols1 is None else cols1)
     cols2 = list(DEFAULT_INTERVAL_COLUMNS if cols2 is None else cols2)
     t1, t2 = A.to_arrow(df1), A.to_arrow(df2)
     probe, build, n_contigs, dictionary = A.encode_keys(t1, cols1, t2, cols2, with_dictionary=True)
-    return t1, t2, probe, build, n_contigs, (cols1[0], probe[0], cols2[0], build[0], dictionary)
+    keys = (cols1[0], probe[0], cols2[0], build[0], dictionary, None)
+    if on_cols:
+        for t in (t1, t2):
+            missing = [c for c in on_cols if c not in t.column_names]
+            assert not missing, f"on_cols {missing} not found in {t.column_names}"
+        (codes1, codes2), cards, _, _ = A.encode_on_cols([t1, t2], on_cols)
+        probe, build, groups, table = A.group_sides(probe, build, n_contigs, codes1, codes2, cards, on_cols)
+        n_contigs = max(groups, 1)
+        keys = keys[:5] + (np.ascontiguousarray(table[:, 0]) if groups else np.zeros(1, np.int32),)
+    return t1, t2, probe, build, n_contigs, keys
 
 
 def overlap(
@@ -335,21 +386,26 @@ def overlap(
     HIP engine is always used.  Output: every df1 column + suffixes[0], then every df2
     column + suffixes[1] (src/operation.rs:277-292); ``overlap_output="left"`` returns df1
     columns only, one row per matching pair, or once per df1 row with ``distinct_output``
-    (src/operation.rs:224-233, 294-298)."""
-    _validate_overlap_input(cols1, cols2, on_cols, suffixes, output_type)
+    (src/operation.rs:224-233, 294-298).
+
+    ``on_cols``: further columns both frames must agree on (e.g. ``["strand"]``): pairs are formed within groups of equal
+    (chrom, on values) only; a null on-value matches nothing, like a null chrom."""
+    on_cols = _validate_overlap_input(cols1, cols2, on_cols, suffixes, output_type)
+    _check_on_cols_present(on_cols, df1, df2)
     zero_based = validate_coordinate_systems(df1, df2)
     mode = _parse_overlap_output_mode(overlap_output)
     logger.info("Optimizing into IntervalJoinExec using %s algorithm (executed by the HIP engine)", algorithm)
     if output_type == "polars.LazyFrame":
         lf = _polars_lazy_result(df1, df2, zero_based, limit, overlap_batches, suffixes=suffixes, cols1=cols1, cols2=cols2,
-                                 batch_rows=_low_memory_batch_rows(), overlap_output=overlap_output, distinct_output=distinct_output)
+                                 batch_rows=_low_memory_batch_rows(), overlap_output=overlap_output, distinct_output=distinct_output,
+                                 on_cols=on_cols)
         if lf is not None:
             return lf
     if output_type == "pyarrow.RecordBatchReader" or limit is not None:
         lazy = overlap_batches(df1, df2, suffixes, cols1, cols2, batch_rows=_low_memory_batch_rows(), limit=limit,
-                               overlap_output=overlap_output, distinct_output=distinct_output, as_reader=True)
+                               overlap_output=overlap_output, distinct_output=distinct_output, as_reader=True, on_cols=on_cols)
         return lazy if output_type == "pyarrow.RecordBatchReader" else A.from_arrow(lazy.read_all(), output_type, zero_based)
-    t1, t2, probe, build, n_contigs, keys = _prepare(df1, df2, cols1, cols2)
+    t1, t2, probe, build, n_contigs, keys = _prepare(df1, df2, cols1, cols2, on_cols)
     if mode == OverlapOutputMode.Join and not low_memory and _key_columns_from_device(t1, t2, cols1, cols2):
         try:
             return A.from_arrow(_overlap_join_rows(t1, t2, probe, build, n_contigs, keys, cols1, cols2, suffixes, zero_based, _materialize_on_device()),
@@ -389,19 +445,21 @@ def nearest(
     column order df1+suffix[0], df2+suffix[1], distance: src/operation.rs:170-197).
 
     A df1 row with no candidate on its contig yields one row with null df2 columns and a null
-    distance (unpinned in the reference; tests/test_native.py:133-140 drops such rows)."""
-    _validate_overlap_input(cols1, cols2, on_cols, suffixes, output_type)
+    distance (unpinned in the reference; tests/test_native.py:133-140 drops such rows).  ``on_cols``: the k nearest df2
+    intervals within the df1 row's group of equal (chrom, on values); a row whose group df2 lacks gets the one null row."""
+    on_cols = _validate_overlap_input(cols1, cols2, on_cols, suffixes, output_type)
+    _check_on_cols_present(on_cols, df1, df2)
     zero_based = validate_coordinate_systems(df1, df2)
     if output_type == "polars.LazyFrame":
         lf = _polars_lazy_result(df1, df2, zero_based, limit, nearest_batches, suffixes=suffixes, cols1=cols1, cols2=cols2, k=k, overlap=overlap,
-                                 distance=distance, batch_rows=_low_memory_batch_rows())
+                                 distance=distance, batch_rows=_low_memory_batch_rows(), on_cols=on_cols)
         if lf is not None:
             return lf
     if output_type == "pyarrow.RecordBatchReader" or limit is not None:
         lazy = nearest_batches(df1, df2, suffixes, cols1, cols2, k=k, overlap=overlap, distance=distance,
-                               batch_rows=_low_memory_batch_rows(), limit=limit, as_reader=True)
+                               batch_rows=_low_memory_batch_rows(), limit=limit, as_reader=True, on_cols=on_cols)
         return lazy if output_type == "pyarrow.RecordBatchReader" else A.from_arrow(lazy.read_all(), output_type, zero_based)
-    t1, t2, probe, build, n_contigs, keys = _prepare(df1, df2, cols1, cols2)
+    t1, t2, probe, build, n_contigs, keys = _prepare(df1, df2, cols1, cols2, on_cols)
     idx, dist, nf = default_engine().nearest(probe, build, strict=zero_based, n_contigs=n_contigs, k=int(k),
                                              include_overlaps=bool(overlap))
     return A.from_arrow(_assemble_nearest(t1, t2, idx, dist, nf, suffixes, distance, keys), output_type, zero_based)
@@ -424,22 +482,24 @@ def count_overlaps(
     (tests/test_coordinate_system_metadata.py:1504-1506).  ``naive_query=False`` selects the
     reference's SQL sweep (range_op.py:512-597), which computes the same two-rank formula the
     device kernel uses; both values run the same kernel here, the sweep's output naming
-    (key columns + suffixes[0]) is honoured."""
-    _validate_overlap_input(cols1, cols2, on_cols, suffixes, output_type)
+    (key columns + suffixes[0]) is honoured, followed by the ``on_cols`` (df1's values).  ``on_cols``: only df2 intervals of
+    the df1 row's group of equal (chrom, on values) are counted."""
+    on_cols = _validate_overlap_input(cols1, cols2, on_cols, suffixes, output_type)
+    _check_on_cols_present(on_cols, df1, df2)
     zero_based = validate_coordinate_systems(df1, df2)
     if output_type == "polars.LazyFrame":
         lf = _polars_lazy_result(df1, df2, zero_based, limit, count_overlaps_batches, suffixes=suffixes, cols1=cols1, cols2=cols2,
-                                 batch_rows=_low_memory_batch_rows(), naive_query=naive_query)
+                                 batch_rows=_low_memory_batch_rows(), naive_query=naive_query, on_cols=on_cols)
         if lf is not None:
             return lf
     if output_type == "pyarrow.RecordBatchReader" or limit is not None:
         lazy = count_overlaps_batches(df1, df2, suffixes, cols1, cols2, batch_rows=_low_memory_batch_rows(), limit=limit,
-                                      naive_query=naive_query, as_reader=True)
+                                      naive_query=naive_query, as_reader=True, on_cols=on_cols)
         return lazy if output_type == "pyarrow.RecordBatchReader" else A.from_arrow(lazy.read_all(), output_type, zero_based)
-    t1, t2, probe, build, n_contigs, _keys = _prepare(df1, df2, cols1, cols2)
+    t1, t2, probe, build, n_contigs, _keys = _prepare(df1, df2, cols1, cols2, on_cols)
     counts = default_engine().count_overlaps(probe, build, strict=zero_based, n_contigs=n_contigs)
     c1 = list(DEFAULT_INTERVAL_COLUMNS if cols1 is None else cols1)
-    return A.from_arrow(_assemble_count(t1, counts, naive_query, c1, suffixes), output_type, zero_based)
+    return A.from_arrow(_assemble_count(t1, counts, naive_query, c1, suffixes, on_cols), output_type, zero_based)
 
 
 # ---- sort-scan family (SURVEY.md section 8f row 2) ----------------------------------------------------
@@ -457,10 +517,12 @@ def coverage(
 ):
     """Covered positions of every df1 interval by the union of the df2 intervals (reference:
     range_op.py:342-415; executed by CountOverlapsProvider(coverage=true), src/operation.rs:306-350).
-    Output = df1 columns + ``coverage`` (Int64), df1 row order kept (range_op_helpers.py:214-222, 317-318)."""
-    _validate_overlap_input(cols1, cols2, on_cols, suffixes, output_type)
+    Output = df1 columns + ``coverage`` (Int64), df1 row order kept (range_op_helpers.py:214-222, 317-318).
+    ``on_cols``: only df2 intervals of the df1 row's group of equal (chrom, on values) cover it."""
+    on_cols = _validate_overlap_input(cols1, cols2, on_cols, suffixes, output_type)
+    _check_on_cols_present(on_cols, df1, df2)
     zero_based = validate_coordinate_systems(df1, df2)
-    t1, t2, probe, build, n_contigs, _keys = _prepare(df1, df2, cols1, cols2)
+    t1, t2, probe, build, n_contigs, _keys = _prepare(df1, df2, cols1, cols2, on_cols)
     cov = default_engine().coverage(probe, build, strict=zero_based, n_contigs=n_contigs)
     return A.from_arrow(t1.append_column("coverage", pa.array(cov, type=pa.int64())), output_type, zero_based)
 
@@ -476,19 +538,35 @@ def merge(
     """Merge overlapping intervals (reference: range_op.py:599-657; MergeProvider, src/operation.rs:352-381).
     Output: (chrom, start: Int64, end: Int64, n_intervals: Int64) in (chrom, start) order
     (range_op_helpers.py:78-90).  ``min_dist=0`` merges overlapping intervals only: bookended half-open
-    intervals stay apart (tests/_expected.py:174-181)."""
-    _validate_overlap_input(cols, cols, on_cols, ("_1", "_2"), output_type)
+    intervals stay apart (tests/_expected.py:174-181).
+
+    ``on_cols``: intervals merge only within groups of equal (chrom, on values); output (chrom, start, end, <on_cols...>,
+    n_intervals) in (chrom, on values, start) order; rows with a null on-value are dropped, as rows with a null chrom are."""
+    on_cols = _validate_overlap_input(cols, cols, on_cols, ("_1", "_2"), output_type)
+    _check_on_cols_present(on_cols, df)
     zero_based = validate_coordinate_system_single(df)
     cols = list(DEFAULT_INTERVAL_COLUMNS if cols is None else cols)
     t = A.to_arrow(df)
     side, n_contigs, dictionary = A.encode_frame(t, cols)
-    keep = side[0] >= 0                                   # rows with a null chrom belong to no contig
+    gchrom = None
+    if on_cols:
+        # group ids over (chrom, on values) with the frame as the build side: sorted dictionaries make them ascend in that order
+        (codes,), cards, dicts, _ = A.encode_on_cols([t], on_cols)
+        empty = (np.empty(0, np.int32),) * 3
+        _, side, groups, table = A.group_sides(empty, side, n_contigs, [np.empty(0, np.int32)] * len(on_cols), codes, cards, on_cols)
+        n_contigs, gchrom = max(groups, 1), table
+    keep = side[0] >= 0                                   # rows with a null chrom (or on-value) belong to no contig
     side = tuple(a[keep] for a in side) if not keep.all() else side
     c, s, e, n = default_engine().merge(side, strict=zero_based, n_contigs=n_contigs, min_dist=int(min_dist))
-    res = pa.table({cols[0]: pc.cast(pc.take(dictionary, pa.array(c, type=pa.int32())), pa.string()),
-                    cols[1]: pa.array(s.astype(np.int64)), cols[2]: pa.array(e.astype(np.int64)),
-                    "n_intervals": pa.array(n, type=pa.int64())})
-    return A.from_arrow(res, output_type, zero_based)
+    c = np.ascontiguousarray(c, np.int32)
+    chrom_ids = c if gchrom is None else A.H.take(np.ascontiguousarray(gchrom[:, 0]), c)
+    data = {cols[0]: pc.cast(pc.take(dictionary, pa.array(chrom_ids, type=pa.int32())), pa.string()),
+            cols[1]: pa.array(s.astype(np.int64)), cols[2]: pa.array(e.astype(np.int64))}
+    for j, name in enumerate(on_cols or ()):
+        values = pc.take(dicts[j], pa.array(A.H.take(np.ascontiguousarray(gchrom[:, 1 + j]), c), type=pa.int32()))
+        data[name] = A.cast_on_values(values, t.schema.field(name).type)
+    data["n_intervals"] = pa.array(n, type=pa.int64())
+    return A.from_arrow(pa.table(data), output_type, zero_based)
 
 
 def cluster(
