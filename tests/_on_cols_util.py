@@ -150,10 +150,11 @@ def got_nearest(df):
     return [(int(i), -1 if pd.isna(x) else int(x), -1 if pd.isna(y) else int(y)) for i, x, y in zip(df["id_1"], b, d)]
 
 
-def check_ops(df1, df2, on_cols, outputs=("pandas.DataFrame", "pyarrow.Table", "pyarrow.RecordBatchReader"), batch_rows=(97,)):
-    """Every operation with ``on_cols`` through the front door (every output kind, the _batches forms) == the per-group oracle."""
-    ep, eb = expected_pairs(df1, df2, on_cols)
-    ec = expected_counts(df1, df2, on_cols)
+def check_ops(df1, df2, on_cols, outputs=("pandas.DataFrame", "pyarrow.Table", "pyarrow.RecordBatchReader"), batch_rows=(97,), strict=True):
+    """Every operation with ``on_cols`` through the front door (every output kind, the _batches forms) == the per-group oracle.
+    ``strict``: the frames' coordinate system (True: 0-based half-open, False: 1-based closed)."""
+    ep, eb = expected_pairs(df1, df2, on_cols, strict)
+    ec = expected_counts(df1, df2, on_cols, strict)
     for out in outputs:
         res = to_pandas(pb.overlap(df1, df2, on_cols=on_cols, output_type=out))
         gp, gb = got_pairs(res)
@@ -171,16 +172,16 @@ def check_ops(df1, df2, on_cols, outputs=("pandas.DataFrame", "pyarrow.Table", "
         for k in (1, 3):
             for ov in (True, False):
                 got = got_nearest(to_pandas(pb.nearest(df1, df2, on_cols=on_cols, k=k, overlap=ov, output_type=out)))
-                assert got == expected_nearest(df1, df2, on_cols, k, ov), f"nearest k={k} overlap={ov} {out}"
+                assert got == expected_nearest(df1, df2, on_cols, k, ov, strict), f"nearest k={k} overlap={ov} {out}"
     cov = pb.coverage(df1, df2, on_cols=on_cols, output_type="pandas.DataFrame")
-    assert (cov["coverage"].to_numpy() == expected_coverage(df1, df2, on_cols)).all()
+    assert (cov["coverage"].to_numpy() == expected_coverage(df1, df2, on_cols, strict)).all()
     m = pb.merge(df1, on_cols=on_cols, output_type="pandas.DataFrame")
     assert list(m.columns) == ["chrom", "start", "end"] + list(on_cols) + ["n_intervals"]
-    assert [tuple(r) for r in m.itertuples(index=False, name=None)] == expected_merge(df1, on_cols)
+    assert [tuple(r) for r in m.itertuples(index=False, name=None)] == expected_merge(df1, on_cols, strict)
     for br in batch_rows:
         gp, gb = got_pairs(concat_batches(pb.overlap_batches(df1, df2, on_cols=on_cols, batch_rows=br)))
         assert (gp == ep).all() and (gb == eb).all(), "overlap_batches"
         c = concat_batches(pb.count_overlaps_batches(df1, df2, on_cols=on_cols, batch_rows=br))
         assert (c["count"].to_numpy() == ec).all(), "count_overlaps_batches"
         got = got_nearest(concat_batches(pb.nearest_batches(df1, df2, on_cols=on_cols, k=3, batch_rows=br)))
-        assert got == expected_nearest(df1, df2, on_cols, 3, True), "nearest_batches"
+        assert got == expected_nearest(df1, df2, on_cols, 3, True, strict), "nearest_batches"

@@ -179,3 +179,60 @@ class _OracleStream:
 
     def close(self):
         self.queue = []
+
+
+# ---- sparse numpy reference of overlap / count_overlaps (independent of the C oracle) ------------------------------------
+
+def _lt(x, y, strict):
+    return x < y if strict else x <= y
+
+
+def sparse_overlap(probe, build, n_contigs, strict, block=1 << 23):
+    """Pairs of overlap by contig grouping: each probe row is expanded against the build rows of its own contig only and the
+    candidates are filtered with the brute-force predicate (Strict: qs < be and bs < qe; Weak: <=).  Contig ids outside
+    [0, n_contigs) never match.  The probes are expanded in blocks of about `block` candidates, so every input size runs in
+    bounded memory.  -> (probe_idx, build_idx) in the oracle's order: probe row, then (build start, build row)."""
+    pc, ps, pe = (np.asarray(a, np.int64) for a in probe)
+    bc, bs, be = (np.asarray(a, np.int64) for a in build)
+    pin = np.nonzero((pc >= 0) & (pc < n_contigs))[0]
+    bin_ = np.nonzero((bc >= 0) & (bc < n_contigs))[0]
+    bin_ = bin_[np.argsort(bc[bin_], kind="stable")]
+    cs = bc[bin_]
+    lo_all = np.searchsorted(cs, pc[pin], "left")
+    k_all = np.searchsorted(cs, pc[pin], "right") - lo_all
+    ends = np.cumsum(k_all)
+    cuts = np.unique(np.concatenate([[0], np.searchsorted(ends, np.arange(block, int(ends[-1]) if len(ends) else 0, block), "right"), [len(pin)]]))
+    outp, outb = [np.empty(0, np.int64)], [np.empty(0, np.int64)]
+    for a, z in zip(cuts[:-1], cuts[1:]):
+        lo, k = lo_all[a:z], k_all[a:z]
+        qp = np.repeat(pin[a:z], k)                                  # one candidate per (probe, build row of its contig)
+        run = np.repeat(lo - (np.cumsum(k) - k), k)                   # candidate j of probe i -> position lo[i] + j
+        qb = bin_[np.arange(len(qp), dtype=np.int64) + run]
+        hit = _lt(ps[qp], be[qb], strict) & _lt(bs[qb], pe[qp], strict)
+        outp.append(qp[hit])
+        outb.append(qb[hit])
+    qp, qb = np.concatenate(outp), np.concatenate(outb)
+    o = np.lexsort((qb, bs[qb], qp))
+    return qp[o].astype(np.int32), qb[o].astype(np.int32)
+
+
+def sparse_count_overlaps(probe, build, n_contigs, strict):
+    p, _ = sparse_overlap(probe, build, n_contigs, strict)
+    return np.bincount(p, minlength=len(probe[0])).astype(np.int64)
+
+
+def sparse_side(rng, n, n_contigs, occupied, span, max_len, lo=0):
+    """Rows on `occupied` random contigs of a dictionary of `n_contigs` (ids 0 and n_contigs - 1 always among them): a few
+    contigs hold thousands of rows, many hold one, the rest of the dictionary is empty.  Starts in [lo, lo + span)."""
+    occ = rng.choice(n_contigs, size=min(occupied, n_contigs), replace=False)
+    occ[:2] = [0, n_contigs - 1][:len(occ[:2])]
+    w = np.ones(len(occ))
+    w[2:6] = n / 8                                                   # heavy contigs
+    c = rng.choice(occ, size=n, p=w / w.sum())
+    c[:len(occ)] = occ[:n]                                           # every chosen contig holds at least one row
+    s = lo + rng.integers(0, span, n, dtype=np.int64)
+    ln = rng.integers(0, max_len + 1, n)
+    long_mask = rng.random(n) < 0.02
+    ln[long_mask] = rng.integers(0, span // 4 + 1, int(long_mask.sum()))
+    e = np.minimum(s + ln, np.iinfo(np.int32).max)
+    return c.astype(np.int32), s.astype(np.int32), e.astype(np.int32)

@@ -166,3 +166,22 @@ def test_full_size_stranded_overlap_100M_x_5M():
     assert len(p) == total
     assert int(b.astype(np.int64).sum()) == checksum
     assert (ps[p] == bs[b]).all() and (probe[0][p] == build[0][b]).all()
+
+
+@pytest.mark.parametrize("zero_based", [True, False])
+@pytest.mark.parametrize("n_samples", [3000, 20_000])
+def test_more_than_10k_groups_every_operation(n_samples, zero_based):
+    """on_cols=["sample"] over 24 chroms x 3000 samples (group domain 72 k, below 2^18) and 24 x 20 000 (480 k, above it), more
+    than 10 k groups on each side; 0-based (Strict) and 1-based (Weak) frames.  The front door composes the group ids on the
+    host (ivj_host_group_ids); the device mark kernels on both sides of 2^18 are covered by
+    test_device_group_ids_equal_the_host_twin.  Here the joins over the group ids run on the GPU."""
+    rng = np.random.default_rng(90 + n_samples)
+    chroms = [f"chr{i}" for i in range(1, 25)]
+    samples = [f"s{i}" for i in range(n_samples)]
+    df1 = U.frame(rng, 40_000, span=120, max_len=40, chroms=chroms, samples=samples)
+    df2 = U.frame(rng, 30_000, span=120, max_len=40, chroms=chroms, samples=samples)
+    for df in (df1, df2):
+        df["strand"] = "+"                                           # (check_ops compares the strands of every pair)
+        df.attrs["coordinate_system_zero_based"] = zero_based
+    assert len(U.groups(df1, df2, ["sample"])) > 10_000 and len(U.groups(df2, df1, ["sample"])) > 10_000
+    U.check_ops(df1, df2, ["sample"], outputs=("pandas.DataFrame", "pyarrow.Table"), batch_rows=(4096,), strict=zero_based)
