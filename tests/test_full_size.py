@@ -59,14 +59,18 @@ class _Dev:
         self.ptrs = []
 
 
-def _check_pair_properties(hp, hb, probe, build, counts, checksum, what):
+def _check_pair_properties(hp, hb, probe, build, counts, checksum, what, strict=True):
     """Size-independent properties that pin the pair SET and the emission order without a sort:
     P = sum of the oracle's counts; per-probe multiplicities = counts; every pair satisfies the predicate; the
     pairs of one probe row are contiguous and strictly ascending in (build.start, build row) -- so no pair is
-    emitted twice, hence every probe row got exactly its matches; checksum of the build rows = the oracle's."""
+    emitted twice, hence every probe row got exactly its matches; checksum of the build rows = the oracle's.
+    strict=False: the Weak predicate (<=)."""
     assert len(hp) == int(counts.sum()), what
     assert (np.bincount(hp, minlength=len(probe[0])) == counts).all(), what
-    assert (probe[1][hp] < build[2][hb]).all() and (build[1][hb] < probe[2][hp]).all(), what
+    if strict:
+        assert (probe[1][hp] < build[2][hb]).all() and (build[1][hb] < probe[2][hp]).all(), what
+    else:
+        assert (probe[1][hp] <= build[2][hb]).all() and (build[1][hb] <= probe[2][hp]).all(), what
     same = hp[1:] == hp[:-1]
     assert int((~same).sum()) + 1 == int((counts > 0).sum()), (what, "pairs of one probe row are not contiguous")
     s0, s1 = build[1][hb[:-1]], build[1][hb[1:]]
