@@ -168,7 +168,8 @@ int ivj_count_overlaps(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* buil
                        const ivj_opts* opts, int64_t* counts);
 
 /* pb.nearest: for every probe row up to k build rows.  idx/dist: caller
- * buffers of probe->n * k (unused slots -1); n_found: probe->n. */
+ * buffers of probe->n * k (unused slots -1); n_found: probe->n.  Nearest over
+ * rows with start > end (on either side) is unspecified. */
 int ivj_nearest(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build,
                 const ivj_opts* opts, int32_t* idx, int64_t* dist, int32_t* n_found);
 

@@ -124,6 +124,7 @@ def count_overlaps_brute(probe: Side, build: Side, strict: bool):
 
 
 def nearest_brute(probe: Side, build: Side, strict: bool, k: int = 1, include_overlaps: bool = True):
+    """Brute-force nearest.  Nearest over rows with start > end is unspecified (this form and nearest_fast differ there)."""
     idx = np.empty((probe.n, k), np.int32)
     dist = np.empty((probe.n, k), np.int64)
     n = np.empty(probe.n, np.int32)
@@ -204,6 +205,8 @@ def placed(side: "Side", threads: int = 0) -> "Side":
 
 def nearest_fast(ix: Index, probe: Side, strict: bool, k: int = 1, include_overlaps: bool = True,
                  threads: int = 0):
+    """Nearest over the sorted index.  Nearest over rows with start > end is unspecified (this form and nearest_brute differ
+    there)."""
     idx = np.empty((probe.n, k), np.int32)
     dist = np.empty((probe.n, k), np.int64)
     n = np.empty(probe.n, np.int32)
