@@ -61,6 +61,12 @@ extern "C" {
 #define IVJ_FILTER_WEAK   0   /* 1-based closed:    a.start <= b.end && b.start <= a.end */
 #define IVJ_FILTER_STRICT 1   /* 0-based half-open: a.start <  b.end && b.start <  a.end */
 
+/* ivj_opts.nearest_ignore: the classes of candidate a nearest call leaves out.  For one probe every build row of its contig is in
+ * exactly one class -- 0 it overlaps the probe (the filter op's predicate holds), 1 "left": build.start (<) probe.end without an
+ * overlap (the row lies before the probe), 2 "right": everything else (it lies after the probe). */
+#define IVJ_NEAREST_IGNORE_LEFT  1   /* drop class 1: only overlapping rows and rows after the probe are reported  */
+#define IVJ_NEAREST_IGNORE_RIGHT 2   /* drop class 2: only overlapping rows and rows before the probe are reported */
+
 typedef struct ivj_ctx ivj_ctx;      /* one device, one stream, scratch arena */
 typedef struct ivj_index ivj_index;  /* sorted build side resident in HBM */
 
@@ -101,6 +107,15 @@ typedef struct {
     int32_t deterministic;     /* overlap count -> fill pair on the slice path: 1 = the output is identical from run to run (stable
                                   partition behind a histogram pass, +0.7 ms per 100 M probes); 0 = same pairs, the order of the probe rows inside a
                                   bucket tile may differ between runs (the reference leaves the row order unspecified) */
+    int32_t nearest_ignore;    /* nearest only: bit mask of IVJ_NEAREST_IGNORE_LEFT | IVJ_NEAREST_IGNORE_RIGHT, 0 (default) = neither.  The result is
+                                  the undirected one -- candidates ordered by (distance, class, build.start, build row) -- with the rows of the
+                                  ignored classes removed BEFORE the cut to nearest_k: left still beats right at equal distance, distances
+                                  stay non-negative, unused slots are -1.  3 is legal: only overlapping rows can be reported (nothing with
+                                  include_overlaps = 0).  Any other value is IVJ_EINVAL.  The mask is uniform over the probe rows of a call:
+                                  a caller whose rows differ in orientation (strand) makes one call per orientation, with the mask and its
+                                  swap.  Same kernels, same fetches per probe as the undirected call, on every path (partition_mode /
+                                  table_mode keep their meaning).  Every entry that runs nearest from an ivj_opts honours it: ivj_nearest,
+                                  ivj_nearest_dev, ivj_stream_* (IVJ_STREAM_NEAREST), ivj_nearest_allgather_dev, ivj_nearest_arrow_stream[_lazy] */
 } ivj_opts;
 
 /* Result of overlap on the host path: library-owned host buffers. */
@@ -120,10 +135,11 @@ typedef struct {
 /* ---- library / context -------------------------------------------------- */
 /* The structs of this header carry no size field: a host built against another revision of it would hand the library structs of
  * another length.  IVJ_ABI_VERSION is bumped whenever a struct or a signature changes (5: ivj_opts.deterministic, the lazy Arrow
- * entries, the per-probe all-gathers, ivj_host_scatter); a binding checks ivj_abi_version() == the IVJ_ABI_VERSION it was built
+ * entries, the per-probe all-gathers, ivj_host_scatter; 6: ivj_opts.nearest_ignore appended -- the struct grows from 36 to 40 bytes --
+ * and ivj_stream_set_nearest_ignore); a binding checks ivj_abi_version() == the IVJ_ABI_VERSION it was built
  * against right after loading the library (the ctypes binding does: polars_bio_amd/_engine.py::load_library; the Rust sketch in
  * INTEGRATION.md does) and refuses to run otherwise. */
-#define IVJ_ABI_VERSION 5
+#define IVJ_ABI_VERSION 6
 int ivj_abi_version(void);
 const char* ivj_last_error(void);
 const char* ivj_version(void);
@@ -389,6 +405,11 @@ int ivj_stream_open(ivj_ctx* ctx, const ivj_side* build, const ivj_opts* opts, i
 int ivj_stream_submit(ivj_stream* st, const ivj_side* batch, ivj_stream_result* done);
 /* no more input: call until done->batch == -1 */
 int ivj_stream_flush(ivj_stream* st, ivj_stream_result* done);
+/* IVJ_STREAM_NEAREST sessions: the direction mask (ivj_opts.nearest_ignore) of the batches submitted AFTER this call; a batch keeps
+ * the mask it was submitted under, whenever its join runs.  A host whose probe rows differ in orientation submits the two
+ * orientations of a batch as two batches to ONE session -- one copy of the build index in HBM -- with this call in between.
+ * IVJ_EINVAL for a mask outside 0 .. 3 or a session of another operation. */
+int ivj_stream_set_nearest_ignore(ivj_stream* st, int32_t mask);
 void ivj_stream_close(ivj_stream* st);
 
 /* ---- multi-GPU: one rank per GPU, contig sharding, all-gatherv of the result batches over RCCL (xGMI) ---------------- *
@@ -490,7 +511,8 @@ int ivj_overlap_arrow_stream(ivj_ctx* ctx, void* df1_stream, void* df2_stream, c
 int ivj_count_overlaps_arrow_stream(ivj_ctx* ctx, void* df1_stream, void* df2_stream, const char* const* cols1, const char* const* cols2,
                                     const ivj_opts* opts, const char* suffix1, int64_t batch_rows, int64_t limit, void* out_stream);
 /* per df1 row its opts->nearest_k nearest df2 rows (one result row each; a df1 row without any keeps one row with null df2
- * columns), + distance: int64 when with_distance (src/operation.rs:100-200) */
+ * columns), + distance: int64 when with_distance (src/operation.rs:100-200).  opts->nearest_ignore applies to every df1 row alike (here
+ * and in the lazy form): the one-call entries take the uniform mask only; a per-row orientation column is the host's to split on. */
 int ivj_nearest_arrow_stream(ivj_ctx* ctx, void* df1_stream, void* df2_stream, const char* const* cols1, const char* const* cols2,
                              const ivj_opts* opts, const char* suffix1, const char* suffix2, int32_t with_distance, int64_t batch_rows,
                              int64_t limit, void* out_stream);

@@ -151,10 +151,14 @@ __device__ __forceinline__ int bound_lo_near(const IndexView& ix, int a, int hi,
 }
 
 // The answer of one probe from the record of its hi-bound (R = nrec[2 hi], Q = nrec[2 hi + 1]); [a, b) = the contig's segment, b > a.
-template <bool STRICT>
+// IGN (ivj_opts.nearest_ignore, a compile-time constant: the undirected kernels carry no test of it): bit 0 drops the rows before the
+// probe ("left": the record's R.y), bit 1 the rows after it ("right": Q.x); an overlapping row wins whatever the mask.  The record is
+// the same one: a direction costs no fetch, it only removes a candidate from the choice.
+template <bool STRICT, int IGN = 0>
 __device__ __forceinline__ void nearest_k1_resolve(const IndexView& ix, int a, int b, int hi, int32_t s, int32_t e, const int4& R, const int4& Q,
                                                    int32_t& idx, long long& dist, int32_t& found) {
     const bool have_l = hi > a, have_r = hi < b;
+    const bool take_l = !(IGN & 1) && have_l, take_r = !(IGN & 2) && have_r;
     if (have_l && lt_op<STRICT>(s, R.x)) {
         // some row below hi overlaps.  The overlapping row with the smallest (start,row) is the first position whose
         // prefix max satisfies "q.start (<) pmax", i.e. the first row of the earliest prefix-max level above q.start:
@@ -165,17 +169,17 @@ __device__ __forceinline__ void nearest_k1_resolve(const IndexView& ix, int a, i
         dist = 0; found = 1;
     } else {
         const long long dl = (long long)s - (long long)R.x;
-        const long long dr = have_r ? gap_dist(s, e, R.z, R.w) : 0;
-        if (have_l && (!have_r || dl <= dr)) { idx = R.y; dist = dl; found = 1; }
-        else if (have_r) { idx = Q.x; dist = dr; found = 1; }
+        const long long dr = take_r ? gap_dist(s, e, R.z, R.w) : 0;
+        if (take_l && (!take_r || dl <= dr)) { idx = R.y; dist = dl; found = 1; }
+        else if (take_r) { idx = Q.x; dist = dr; found = 1; }
     }
 }
 
 // k = 1, include_overlaps = 1 (the default pb.nearest).  An overlapping row wins with distance 0
 // (the one with the smallest (start,row): tests/_expected.py:130-172 tie-break); otherwise the
 // closer of the row with the largest end before the probe (ties: smallest (start,row)) and the
-// row with the smallest start after it; equal distance -> the left one.
-template <bool STRICT, int N>
+// row with the smallest start after it; equal distance -> the left one.  IGN != 0: the directional forms (nearest_k1_resolve).
+template <bool STRICT, int N, int IGN = 0>
 __global__ __launch_bounds__(PROBE_THREADS) void k_nearest_k1(IndexView ix, const int32_t* __restrict__ pc,
                                                               const int32_t* __restrict__ ps,
                                                               const int32_t* __restrict__ pe, int64_t n, bool vec_ok,
@@ -210,7 +214,7 @@ __global__ __launch_bounds__(PROBE_THREADS) void k_nearest_k1(IndexView ix, cons
     for (int k = 0; k < N; ++k) {
         if (i0 + k >= n) continue;
         int32_t idx = -1; long long dist = -1; int32_t found = 0;
-        if (b[k] > a[k]) nearest_k1_resolve<STRICT>(ix, a[k], b[k], hi[k], s[k], e[k], R[k], Q[k], idx, dist, found);
+        if (b[k] > a[k]) nearest_k1_resolve<STRICT, IGN>(ix, a[k], b[k], hi[k], s[k], e[k], R[k], Q[k], idx, dist, found);
         const int64_t o = out_row ? (int64_t)out_row[i0 + k] : i0 + k;
         if ((ablate & 4) && idx != 123456789) continue;
         out_idx[o] = idx; out_dist[o] = dist; out_n[o] = found;
@@ -221,8 +225,9 @@ __global__ __launch_bounds__(PROBE_THREADS) void k_nearest_k1(IndexView ix, cons
 // 64-byte line per probe (round 5; round 4: 128 bytes) -- the nearest record of the first position of the bin its end falls into AND
 // the three rows from there on, from which the records of the positions hi can take are replayed in registers -- fetched with four
 // independent 16-byte loads; only a bin with a fourth row below the probe's end, or a probe outside its contig's table, takes the
-// second (dependent) gather from nrec.  Per-contig metadata in LDS (n_contigs <= CM_LDS).
-template <bool STRICT, int N>
+// second (dependent) gather from nrec.  Per-contig metadata in LDS (n_contigs <= CM_LDS).  IGN: as nearest_k1_resolve -- the same line, the
+// same leftovers (what a line cannot settle does not depend on the direction), one candidate less in the choice.
+template <bool STRICT, int N, int IGN = 0>
 __global__ __launch_bounds__(PROBE_THREADS, 8) void k_nearest_k1_lines(IndexView ix, const int32_t* __restrict__ pc, const int32_t* __restrict__ ps,
                                                                     const int32_t* __restrict__ pe, int64_t n, bool vec_ok,
                                                                     int32_t* __restrict__ out_idx, long long* __restrict__ out_dist,
@@ -335,6 +340,7 @@ __global__ __launch_bounds__(PROBE_THREADS, 8) void k_nearest_k1_lines(IndexView
         slow[k] = far[k]; deep[k] = false;
         if (i0 + k < n && b[k] > a[k] && !far[k]) {
             const bool have_l = hi[k] > a[k], have_r = hi[k] < b[k];
+            const bool take_l = !(IGN & 1) && have_l, take_r = !(IGN & 2) && have_r;
             if (have_l && lt_op<STRICT>(s[k], R[k].x)) {
                 dist[k] = 0; found[k] = 1;
                 if (!(Q[k].z >= 0 && lt_op<STRICT>(s[k], Q[k].y))) idx[k] = R[k].y;
@@ -346,9 +352,9 @@ __global__ __launch_bounds__(PROBE_THREADS, 8) void k_nearest_k1_lines(IndexView
                 }
             } else {
                 const long long dl = (long long)s[k] - (long long)R[k].x;
-                const long long dr = have_r ? gap_dist(s[k], e[k], R[k].z, R[k].w) : 0;
-                if (have_l && (!have_r || dl <= dr)) { idx[k] = R[k].y; dist[k] = dl; found[k] = 1; }
-                else if (have_r) { idx[k] = Q[k].x; dist[k] = dr; found[k] = 1; }
+                const long long dr = take_r ? gap_dist(s[k], e[k], R[k].z, R[k].w) : 0;
+                if (take_l && (!take_r || dl <= dr)) { idx[k] = R[k].y; dist[k] = dl; found[k] = 1; }
+                else if (take_r) { idx[k] = Q[k].x; dist[k] = dr; found[k] = 1; }
             }
         }
     }
@@ -384,7 +390,7 @@ __global__ __launch_bounds__(PROBE_THREADS, 8) void k_nearest_k1_lines(IndexView
 // REST_WORDS mask words (REST_WORDS x 64 probes), lists the marked probes in LDS (exclusive scan of the popcounts) and works through the
 // list with full wavefronts -- left in place, ~ 3 % of the lanes kept every wavefront alive for the longest dependent chain (0.81 ms).
 constexpr int REST_WORDS = 128;
-template <bool STRICT, int N>
+template <bool STRICT, int N, int IGN = 0>
 __global__ __launch_bounds__(PROBE_THREADS) void k_nearest_k1_rest(IndexView ix, const int32_t* __restrict__ pc, const int32_t* __restrict__ ps,
                                                                    const int32_t* __restrict__ pe, int64_t n, int64_t n_words,
                                                                    const unsigned long long* __restrict__ rest, int32_t* __restrict__ out_idx,
@@ -436,7 +442,7 @@ __global__ __launch_bounds__(PROBE_THREADS) void k_nearest_k1_rest(IndexView ix,
         int32_t idx = -1; long long dist = -1; int32_t found = 0;
         if (b[0] > a[0]) {
             const int4 R = ix.nrec[2 * (int64_t)hi[0]], Q = ix.nrec[2 * (int64_t)hi[0] + 1];
-            nearest_k1_resolve<STRICT>(ix, a[0], b[0], hi[0], s, e[0], R, Q, idx, dist, found);
+            nearest_k1_resolve<STRICT, IGN>(ix, a[0], b[0], hi[0], s, e[0], R, Q, idx, dist, found);
         }
         out_idx[i] = idx; out_dist[i] = dist; out_n[i] = found;
     }
@@ -445,7 +451,10 @@ __global__ __launch_bounds__(PROBE_THREADS) void k_nearest_k1_rest(IndexView ix,
 // General k / include_overlaps: per-probe merge of three ordered streams (overlapping rows in
 // (start,row) order; "left" rows by end descending; "right" rows by start ascending).
 // One thread per probe; k slots per probe, unused slots -1.
-template <bool STRICT>
+// IGN (ivj_opts.nearest_ignore): an ignored stream is switched off at compile time -- bit 0: the left stream is never positioned or
+// advanced (no bound_r, no walk over the runs of e_end / e_pos: the end order is not read at all); bit 1: the right stream's cursor is
+// never read.  The overlap stream is the same in every form.
+template <bool STRICT, int IGN = 0>
 __global__ __launch_bounds__(PROBE_THREADS) void k_nearest_general(IndexView ix, const int32_t* __restrict__ pc,
                                                                    const int32_t* __restrict__ ps,
                                                                    const int32_t* __restrict__ pe, int64_t n, int kk,
@@ -471,23 +480,23 @@ __global__ __launch_bounds__(PROBE_THREADS) void k_nearest_general(IndexView ix,
             const int lo = bound_lo<STRICT>(ix, a, hi, qs);
             hier_walk_up<STRICT>(ix.hier, lo, hi, qs, [&](int p) { oi[found] = ix.b_row[p]; od[found] = 0; ++found; return found < kk; });
         }
-        const int r_top = bound_r<STRICT>(ix, a, b, qs);
+        const int r_top = (IGN & 1) ? a : bound_r<STRICT>(ix, a, b, qs);
         int run_hi = r_top, run_lo = r_top, lp = r_top, rp = hi;
         while (found < kk) {
-            for (;;) {
+            if (!(IGN & 1)) for (;;) {
                 while (lp < run_hi && ix.e_pos[lp] >= hi) ++lp;   // not class "left": start fails (<) q.end
                 if (lp < run_hi || run_lo <= a) break;
                 run_hi = run_lo;
                 run_lo = bsearch32<false>(ix.e_end, a, run_hi, ix.e_end[run_hi - 1]);
                 lp = run_lo;
             }
-            const bool have_l = lp < run_hi, have_r = rp < b;
+            const bool have_l = !(IGN & 1) && lp < run_hi, have_r = !(IGN & 2) && rp < b;
             if (!have_l && !have_r) break;
             long long dl = 0, dr = 0; int pl = 0;
             if (have_l) { pl = ix.e_pos[lp]; dl = gap_dist(qs, qe, ix.b_start[pl], ix.ep[pl].x); }
             if (have_r) dr = gap_dist(qs, qe, ix.b_start[rp], ix.ep[rp].x);
             if (have_l && (!have_r || dl <= dr)) { oi[found] = ix.b_row[pl]; od[found] = dl; ++found; ++lp; }
-            else { oi[found] = ix.b_row[rp]; od[found] = dr; ++found; ++rp; }
+            else if (!(IGN & 2)) { oi[found] = ix.b_row[rp]; od[found] = dr; ++found; ++rp; }
         }
     }
     out_n[o] = found;

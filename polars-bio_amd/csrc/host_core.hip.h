@@ -435,6 +435,8 @@ int check_opts(const ivj_opts* o) {
     if (o->partition_mode < 0 || o->partition_mode > 6 || o->partition_mode == 3 || o->partition_mode == 4)
         return fail(IVJ_EINVAL, "partition_mode must be 0 (auto), 1 (256-way buckets), 2 (never), 5 (flat, fused path only) or 6 (LDS-resident index slices)");
     if (o->slice_rows < 0 || o->slice_chunk < 0) return fail(IVJ_EINVAL, "slice_rows / slice_chunk must be >= 0");
+    if (o->nearest_ignore < 0 || o->nearest_ignore > (IVJ_NEAREST_IGNORE_LEFT | IVJ_NEAREST_IGNORE_RIGHT))
+        return fail(IVJ_EINVAL, "nearest_ignore must be 0 or a mask of IVJ_NEAREST_IGNORE_LEFT (1) and IVJ_NEAREST_IGNORE_RIGHT (2)");
     return IVJ_OK;
 }
 int check_side(const ivj_side* s, const char* what) {

@@ -349,7 +349,27 @@ int count_overlaps_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe, const
     return IVJ_OK;
 }
 
+// One nearest kernel, instantiated for the filter op and for the direction mask (ivj_opts.nearest_ignore): the mask is a template
+// argument, so the undirected call launches the very instantiation it always did and no kernel tests the mask per probe.
+#define LAUNCH_NEAREST(ctx, name, KERNEL, PRE, grid, block, ...)                                                                        \
+    do {                                                                                                                               \
+        switch ((strict ? 4 : 0) | ign) {                                                                                              \
+        case 0: LAUNCH(ctx, name, (KERNEL<false PRE, 0>), grid, block, __VA_ARGS__); break;                                            \
+        case 1: LAUNCH(ctx, name "_noleft", (KERNEL<false PRE, 1>), grid, block, __VA_ARGS__); break;                                  \
+        case 2: LAUNCH(ctx, name "_noright", (KERNEL<false PRE, 2>), grid, block, __VA_ARGS__); break;                                 \
+        case 3: LAUNCH(ctx, name "_ovonly", (KERNEL<false PRE, 3>), grid, block, __VA_ARGS__); break;                                  \
+        case 4: LAUNCH(ctx, name, (KERNEL<true PRE, 0>), grid, block, __VA_ARGS__); break;                                             \
+        case 5: LAUNCH(ctx, name "_noleft", (KERNEL<true PRE, 1>), grid, block, __VA_ARGS__); break;                                   \
+        case 6: LAUNCH(ctx, name "_noright", (KERNEL<true PRE, 2>), grid, block, __VA_ARGS__); break;                                  \
+        default: LAUNCH(ctx, name "_ovonly", (KERNEL<true PRE, 3>), grid, block, __VA_ARGS__); break;                                  \
+        }                                                                                                                              \
+    } while (0)
+#define NEAREST_ITEMS , PROBE_ITEMS_LAT
+
+// The path choice (record / bucketed record / lines / general) does not look at the direction mask: a direction removes candidates
+// from the choice a kernel makes, never a fetch, so what pays for the undirected call pays for the directed one.
 int nearest_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe, const ivj_opts* opts, int32_t* idx, int64_t* dist, int32_t* nf) {
+    const int ign = opts->nearest_ignore & 3;                  // check_opts of every entry refused anything outside 0 .. 3
     IVJ_TRY(need_tables(ctx, ix));
     const int64_t n = probe->n;
     const int k = opts->nearest_k < 1 ? 1 : opts->nearest_k;
@@ -357,7 +377,10 @@ int nearest_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe, const ivj_op
     const bool strict = opts->filter_op == IVJ_FILTER_STRICT;
     const bool k1 = k == 1 && opts->include_overlaps;
     if (k1) IVJ_TRY(build_argmax(ctx, ix));
-    else { IVJ_TRY(build_end_order(ctx, ix)); IVJ_TRY(ensure_hier(ctx, ix)); }     // nearest_general lists overlapping rows with hier_walk_up
+    else {
+        if (!(ign & 1)) IVJ_TRY(build_end_order(ctx, ix));                         // the left stream walks the end order; ignored, nothing reads it
+        IVJ_TRY(ensure_hier(ctx, ix));                                             // nearest_general lists overlapping rows with hier_walk_up
+    }
     // large probe sides: bucket them by genomic position first (every gather of the kernel then stays in the
     // XCD L2s); the kernels write each result to the probe's original row
     const int32_t *qc = probe->contig, *qs = probe->start, *qe = probe->end, *qrow = nullptr;
@@ -380,11 +403,9 @@ int nearest_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe, const ivj_op
         const int64_t n_words = nwf * PROBE_ITEMS_LAT;
         IVJ_TRY(arena_reserve(ctx, align_up((size_t)n_words * 16) + 4096));
         unsigned long long* rest = arena_take<unsigned long long>(ctx, 2 * n_words);
-        if (strict) LAUNCH(ctx, "nearest_k1_lines", (k_nearest_k1_lines<true, PROBE_ITEMS_LAT>), tiles, PROBE_THREADS, v, qc, qs, qe, n, vec, idx, (long long*)dist, nf, rest, n_words);
-        else LAUNCH(ctx, "nearest_k1_lines", (k_nearest_k1_lines<false, PROBE_ITEMS_LAT>), tiles, PROBE_THREADS, v, qc, qs, qe, n, vec, idx, (long long*)dist, nf, rest, n_words);
+        LAUNCH_NEAREST(ctx, "nearest_k1_lines", k_nearest_k1_lines, NEAREST_ITEMS, tiles, PROBE_THREADS, v, qc, qs, qe, n, vec, idx, (long long*)dist, nf, rest, n_words);
         const int64_t rgrid = (n_words + REST_WORDS - 1) / REST_WORDS;
-        if (strict) LAUNCH(ctx, "nearest_k1_rest", (k_nearest_k1_rest<true, PROBE_ITEMS_LAT>), rgrid, PROBE_THREADS, v, qc, qs, qe, n, n_words, (const unsigned long long*)rest, idx, (long long*)dist, nf);
-        else LAUNCH(ctx, "nearest_k1_rest", (k_nearest_k1_rest<false, PROBE_ITEMS_LAT>), rgrid, PROBE_THREADS, v, qc, qs, qe, n, n_words, (const unsigned long long*)rest, idx, (long long*)dist, nf);
+        LAUNCH_NEAREST(ctx, "nearest_k1_rest", k_nearest_k1_rest, NEAREST_ITEMS, rgrid, PROBE_THREADS, v, qc, qs, qe, n, n_words, (const unsigned long long*)rest, idx, (long long*)dist, nf);
         HIP_TRY(hipGetLastError());
         return IVJ_OK;
     }
@@ -409,20 +430,20 @@ int nearest_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe, const ivj_op
             IVJ_TRY(arena_reserve(ctx, 2 * align_up((size_t)n * 4) + align_up((size_t)n * 8) + 4096));
             o_idx = arena_take<int32_t>(ctx, n); o_nf = arena_take<int32_t>(ctx, n); o_dist = arena_take<long long>(ctx, n);
         }
-        if (strict) LAUNCH(ctx, "nearest_k1", (k_nearest_k1<true, PROBE_ITEMS_LAT>), 8 * ((tiles + 7) / 8), PROBE_THREADS, v, qc, qs, qe, n, vec, (const int32_t*)nullptr, o_idx, o_dist, o_nf, ctx->env_count_ablate);
-        else LAUNCH(ctx, "nearest_k1", (k_nearest_k1<false, PROBE_ITEMS_LAT>), 8 * ((tiles + 7) / 8), PROBE_THREADS, v, qc, qs, qe, n, vec, (const int32_t*)nullptr, o_idx, o_dist, o_nf, ctx->env_count_ablate);
+        LAUNCH_NEAREST(ctx, "nearest_k1", k_nearest_k1, NEAREST_ITEMS, 8 * ((tiles + 7) / 8), PROBE_THREADS, v, qc, qs, qe, n, vec, (const int32_t*)nullptr, o_idx, o_dist, o_nf, ctx->env_count_ablate);
         if (qrow) {
             // n_found of k = 1 is "a row was found": derived from the row index while it is written
             UnpermuteCols uc{{o_idx, o_dist, nullptr}, {idx, dist, nullptr}, {4, 8, 0}, 2, nf};
             IVJ_TRY(unpermute(ctx, n, uc));
         }
     } else {
-        if (strict) LAUNCH(ctx, "nearest_general", (k_nearest_general<true>), grid1d(n, PROBE_THREADS), PROBE_THREADS, v, qc, qs, qe, n, k, (int)opts->include_overlaps, qrow, idx, (long long*)dist, nf);
-        else LAUNCH(ctx, "nearest_general", (k_nearest_general<false>), grid1d(n, PROBE_THREADS), PROBE_THREADS, v, qc, qs, qe, n, k, (int)opts->include_overlaps, qrow, idx, (long long*)dist, nf);
+        LAUNCH_NEAREST(ctx, "nearest_general", k_nearest_general, , grid1d(n, PROBE_THREADS), PROBE_THREADS, v, qc, qs, qe, n, k, (int)opts->include_overlaps, qrow, idx, (long long*)dist, nf);
     }
     HIP_TRY(hipGetLastError());
     return IVJ_OK;
 }
+#undef NEAREST_ITEMS
+#undef LAUNCH_NEAREST
 
 // host side -> device copies of one side
 struct DevSide {

@@ -27,6 +27,7 @@ struct ivj_stream {
         char* h_out = nullptr; size_t h_out_cap = 0;     // pinned
         hipEvent_t ev_h2d = nullptr, ev_join = nullptr, ev_d2h = nullptr;
         int state = 0;                       // 0 free, 1 H2D enqueued, 2 D2H enqueued
+        int32_t ignore = 0;                  // nearest: opts.nearest_ignore as it stood when the batch was submitted
     } slot[3];
     int64_t submitted = 0, joined = 0, delivered = 0;
     int64_t pair_hint = 0;                   // pairs of the last overlap batch (capacity guess of the fused pass)
@@ -82,7 +83,8 @@ int stream_join_slot(ivj_stream* st, int s) {
         const size_t slots = (size_t)n * (size_t)st->k;
         const size_t o_dist = align_up(slots * 4, 8), o_nf = o_dist + slots * 8;
         IVJ_TRY(stream_grow(&S.d_out, &S.d_out_cap, o_nf + (size_t)n * 4, false));
-        IVJ_TRY(nearest_dev(ctx, st->ix, &side, &st->opts, (int32_t*)S.d_out, (int64_t*)(S.d_out + o_dist), (int32_t*)(S.d_out + o_nf)));
+        ivj_opts o = st->opts; o.nearest_ignore = S.ignore;                   // the join runs one submit later: the mask was latched with the batch
+        IVJ_TRY(nearest_dev(ctx, st->ix, &side, &o, (int32_t*)S.d_out, (int64_t*)(S.d_out + o_dist), (int32_t*)(S.d_out + o_nf)));
         S.n_out = n;
         out_bytes = o_nf + (size_t)n * 4;
     }
@@ -132,7 +134,7 @@ int stream_turn(ivj_stream* st, const ivj_side* batch, ivj_stream_result* done) 
                 HIP_TRY(hipMemcpyAsync((char*)S.d_in + c * col, (char*)S.h_in + c * col, nb, hipMemcpyHostToDevice, st->s_h2d));
         }
         HIP_TRY(hipEventRecord(S.ev_h2d, st->s_h2d));
-        S.id = st->submitted; S.n = batch->n; S.n_out = 0; S.state = 1;
+        S.id = st->submitted; S.n = batch->n; S.n_out = 0; S.state = 1; S.ignore = st->opts.nearest_ignore;
         ++st->submitted;
     }
     // join the oldest batch whose columns are on their way (the host blocks here while the copy engines work)

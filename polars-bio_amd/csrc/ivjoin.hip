@@ -971,6 +971,15 @@ int ivj_stream_flush(ivj_stream* st, ivj_stream_result* done) try {
     return stream_turn(st, nullptr, done);
 } IVJ_ABI_CATCH
 
+int ivj_stream_set_nearest_ignore(ivj_stream* st, int32_t mask) try {
+    if (!st) return fail(IVJ_EINVAL, "stream is NULL");
+    if (st->op != IVJ_STREAM_NEAREST) return fail(IVJ_EINVAL, "ivj_stream_set_nearest_ignore needs an IVJ_STREAM_NEAREST session");
+    if (mask < 0 || mask > (IVJ_NEAREST_IGNORE_LEFT | IVJ_NEAREST_IGNORE_RIGHT))
+        return fail(IVJ_EINVAL, "nearest_ignore must be 0 or a mask of IVJ_NEAREST_IGNORE_LEFT (1) and IVJ_NEAREST_IGNORE_RIGHT (2)");
+    st->opts.nearest_ignore = mask;
+    return IVJ_OK;
+} IVJ_ABI_CATCH
+
 namespace {
 // device / pinned resources of a streaming session; the staging goes back to the context's cache when it is still there
 void stream_release(ivj_stream* st, bool keep_cache) {

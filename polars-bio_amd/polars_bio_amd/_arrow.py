@@ -506,6 +506,18 @@ def _is_stringish(t: pa.DataType) -> bool:
             or (hasattr(pa.types, "is_string_view") and pa.types.is_string_view(t)))
 
 
+def minus_rows(col) -> np.ndarray:
+    """bool per row of a direction column (nearest's ``direction_col``): True where the value is the string "-".  Every other
+    value -- "+", ".", a null, a column that holds no strings at all -- reads as "+"."""
+    if pa.types.is_dictionary(col.type):
+        col = pc.cast(col, col.type.value_type)
+    if len(col) == 0 or not _is_stringish(col.type):
+        return np.zeros(len(col), bool)
+    m = pc.fill_null(pc.equal(col, "-"), False)
+    m = m.combine_chunks() if isinstance(m, pa.ChunkedArray) else m
+    return np.asarray(m.to_numpy(zero_copy_only=False), dtype=bool)
+
+
 def on_col_type(name: str, *types) -> pa.DataType:
     """The one type the values of on_col ``name`` are compared in across the frames: strings (any string type, or a
     dictionary / categorical of strings) as large_string, integers (or dictionaries of integers) as int64, any other type only

@@ -32,7 +32,7 @@ ABI_SYMBOLS = [
     "ivj_side_from_arrow", "ivj_materialize_dev", "ivj_overlap_fused_rows_dev", "ivj_take_dev", "ivj_take", "ivj_overlap_rows", "ivj_rows_free", "ivj_rows_export_arrow",
     "ivj_subtract", "ivj_complement", "ivj_pieces_free", "ivj_subtract_dev",
     "ivj_merge", "ivj_merged_free", "ivj_cluster", "ivj_coverage", "ivj_cluster_dev", "ivj_merge_dev", "ivj_coverage_dev",
-    "ivj_stream_open", "ivj_stream_submit", "ivj_stream_flush", "ivj_stream_close",
+    "ivj_stream_open", "ivj_stream_submit", "ivj_stream_flush", "ivj_stream_set_nearest_ignore", "ivj_stream_close",
     "ivj_dev_alloc", "ivj_dev_free", "ivj_memcpy_h2d", "ivj_memcpy_d2h",
     "ivj_comm_unique_id", "ivj_comm_create", "ivj_comm_create_local", "ivj_comm_destroy", "ivj_comm_info",
     "ivj_allgather_counts", "ivj_allgatherv_dev", "ivj_overlap_allgather_dev",
@@ -44,8 +44,10 @@ ABI_SYMBOLS = [
     "ivj_host_narrow_i32", "ivj_host_encode_utf8", "ivj_host_encode_keys64", "ivj_host_remap_i32", "ivj_host_take", "ivj_host_scatter", "ivj_host_widen_i32",
 ]
 
-ABI_VERSION = 5            # include/ivjoin.h: IVJ_ABI_VERSION (struct layouts and signatures this binding assumes)
+ABI_VERSION = 6            # include/ivjoin.h: IVJ_ABI_VERSION (struct layouts and signatures this binding assumes)
 STREAM_OVERLAP, STREAM_COUNT, STREAM_NEAREST = 0, 1, 2
+# ivj_opts.nearest_ignore: the candidate classes a nearest call leaves out (rows before / after the probe; overlapping rows always count)
+NEAREST_IGNORE_LEFT, NEAREST_IGNORE_RIGHT = 1, 2
 
 ROW_COLUMNS = ("probe_idx", "build_idx", "contig", "start_1", "end_1", "start_2", "end_2")
 
@@ -82,7 +84,7 @@ class _ArrowKeys(C.Structure):
 class _Opts(C.Structure):
     _fields_ = [("filter_op", C.c_int32), ("n_contigs", C.c_int32), ("nearest_k", C.c_int32),
                 ("include_overlaps", C.c_int32), ("partition_mode", C.c_int32), ("table_mode", C.c_int32), ("slice_rows", C.c_int32), ("slice_chunk", C.c_int32),
-                ("deterministic", C.c_int32)]
+                ("deterministic", C.c_int32), ("nearest_ignore", C.c_int32)]
 
 
 class _Pairs(C.Structure):
@@ -195,6 +197,7 @@ def load_library() -> C.CDLL:
         L.ivj_stream_open.argtypes = [vp, P, O, C.c_int, C.c_int64, C.POINTER(vp)]
         L.ivj_stream_submit.argtypes = [vp, P, C.POINTER(_StreamResult)]
         L.ivj_stream_flush.argtypes = [vp, C.POINTER(_StreamResult)]
+        L.ivj_stream_set_nearest_ignore.argtypes = [vp, C.c_int32]
         L.ivj_stream_close.argtypes = [vp]
         L.ivj_stream_close.restype = None
         L.ivj_dev_alloc.argtypes = [vp, C.c_int64, C.POINTER(vp)]
@@ -280,9 +283,17 @@ def side_from_arrow(batch) -> Tuple[_Side, tuple]:
     return side, (batch, arr, sch)
 
 
+def _ignore_mask(mask) -> int:
+    mask = int(mask)
+    if mask < 0 or mask > (NEAREST_IGNORE_LEFT | NEAREST_IGNORE_RIGHT):
+        raise ValueError(f"nearest_ignore must be 0 or a mask of NEAREST_IGNORE_LEFT (1) and NEAREST_IGNORE_RIGHT (2), got {mask}")
+    return mask
+
+
 def make_opts(strict: bool, n_contigs: int, k: int = 1, include_overlaps: bool = True, partition_mode: int = 0,
-              table_mode: int = 0, slice_rows: int = 0, slice_chunk: int = 0, deterministic: bool = False) -> _Opts:
+              table_mode: int = 0, slice_rows: int = 0, slice_chunk: int = 0, deterministic: bool = False, nearest_ignore: int = 0) -> _Opts:
     o = _Opts()
+    o.nearest_ignore = _ignore_mask(nearest_ignore)
     o.deterministic = 1 if deterministic else 0
     o.slice_rows = int(slice_rows)
     o.slice_chunk = int(slice_chunk)
@@ -347,12 +358,13 @@ class ProbeStream:
         count_overlaps  ``counts``
         nearest         ``build_idx`` (n_probe x k, -1 = none), ``dist`` (n_probe x k), ``n_found``
     The arrays are copies unless ``copy=False`` (then they view the stream's pinned result slot and are valid until the
-    next call on the stream)."""
+    next call on the stream).  nearest: ``nearest_ignore`` is the direction mask of the first batches, set_nearest_ignore()
+    changes it for the batches submitted after the call."""
 
     def __init__(self, engine: "Engine", build, strict: bool, n_contigs: int, op: int, max_batch_rows: int, k: int = 1,
-                 include_overlaps: bool = True, partition_mode: int = 0, copy: bool = True):
+                 include_overlaps: bool = True, partition_mode: int = 0, copy: bool = True, nearest_ignore: int = 0):
         self.engine, self.op, self.k, self.copy = engine, int(op), int(k), copy
-        self.opts = make_opts(strict, n_contigs, k, include_overlaps, partition_mode=partition_mode)
+        self.opts = make_opts(strict, n_contigs, k, include_overlaps, partition_mode=partition_mode, nearest_ignore=nearest_ignore)
         bs, keep = _host_side(*build)
         h = C.c_void_p()
         _check(engine.L, engine.L.ivj_stream_open(engine.h, C.byref(bs), C.byref(self.opts), self.op, int(max_batch_rows), C.byref(h)),
@@ -395,6 +407,13 @@ class ProbeStream:
         _check(self.engine.L, self.engine.L.ivj_stream_submit(self.h, C.byref(side), C.byref(r)), "ivj_stream_submit")
         del keep
         return self._result(r)
+
+    def set_nearest_ignore(self, mask: int):
+        """Direction mask (NEAREST_IGNORE_LEFT | NEAREST_IGNORE_RIGHT) of the batches submitted from now on; a batch already
+        submitted keeps the mask it was submitted under."""
+        mask = _ignore_mask(mask)
+        _check(self.engine.L, self.engine.L.ivj_stream_set_nearest_ignore(self.h, mask), "ivj_stream_set_nearest_ignore")
+        self.opts.nearest_ignore = mask
 
     def flush(self):
         r = _StreamResult()
@@ -606,13 +625,15 @@ class Engine:
         return counts
 
     def nearest(self, probe, build, strict: bool, n_contigs: int, k: int = 1, include_overlaps: bool = True,
-                table_mode: int = 0, partition_mode: int = 0):
-        """partition_mode 0 auto / 1 bucket the probe side first / 2 never: same result, probe order kept."""
+                table_mode: int = 0, partition_mode: int = 0, nearest_ignore: int = 0):
+        """partition_mode 0 auto / 1 bucket the probe side first / 2 never: same result, probe order kept.
+        nearest_ignore: NEAREST_IGNORE_LEFT (1) leaves out the rows before the probe, NEAREST_IGNORE_RIGHT (2) the rows after it
+        (overlapping rows always count); the rest of the ordered candidate list, cut to k."""
         ps, keep_p = _host_side(*probe)
         bs, keep_b = _host_side(*build)
         if k < 1:
             raise ValueError("k must be >= 1")
-        o = make_opts(strict, n_contigs, k, include_overlaps, table_mode=table_mode, partition_mode=partition_mode)
+        o = make_opts(strict, n_contigs, k, include_overlaps, table_mode=table_mode, partition_mode=partition_mode, nearest_ignore=nearest_ignore)
         idx = np.empty((ps.n, k), np.int32)
         dist = np.empty((ps.n, k), np.int64)
         nf = np.empty(ps.n, np.int32)
@@ -766,9 +787,9 @@ class Engine:
 
     # ---- streaming: build side resident, probe side in bounded batches ---------
     def probe_stream(self, build, strict: bool, n_contigs: int, op: int = STREAM_OVERLAP, max_batch_rows: int = 8_000_000, k: int = 1,
-                     include_overlaps: bool = True, partition_mode: int = 0, copy: bool = True) -> ProbeStream:
+                     include_overlaps: bool = True, partition_mode: int = 0, copy: bool = True, nearest_ignore: int = 0) -> ProbeStream:
         """Open a streaming probe session (ivj_stream_open): see ProbeStream."""
-        return ProbeStream(self, build, strict, n_contigs, op, max_batch_rows, k, include_overlaps, partition_mode, copy)
+        return ProbeStream(self, build, strict, n_contigs, op, max_batch_rows, k, include_overlaps, partition_mode, copy, nearest_ignore)
 
     def overlap_batches(self, probe, build, strict: bool, n_contigs: int, batch_rows: int = 8_000_000):
         """Generator of (probe_idx, build_idx) numpy batches over a probe side that is already in host arrays.
@@ -957,10 +978,10 @@ def arrow_take_stream(src, idx, batch_rows: int = 0):
 
 
 def _arrow_stream_call(engine, op: str, df1, df2, cols1, cols2, strict: bool, suffixes, k: int = 1, include_overlaps: bool = True,
-                       distance: bool = True, batch_rows: int = 0, limit=None, lazy: bool = False, max_batch_rows: int = 0):
+                       distance: bool = True, batch_rows: int = 0, limit=None, lazy: bool = False, max_batch_rows: int = 0, nearest_ignore: int = 0):
     L = load_library()
+    opts = make_opts(strict, 0, k, include_overlaps, nearest_ignore=nearest_ignore)
     s1, s2, out = _export_stream(df1), _export_stream(df2), _ArrowStream()
-    opts = make_opts(strict, 0, k, include_overlaps)
     lim = -1 if limit is None else int(limit)
     sfx = [None if x is None else str(x).encode() for x in suffixes]
     a = (engine.h, C.addressof(s1), C.addressof(s2), _names3(cols1), _names3(cols2), C.byref(opts))
@@ -1006,8 +1027,10 @@ def count_overlaps_arrow_stream(engine, df1, df2, strict: bool, cols1=None, cols
 
 
 def nearest_arrow_stream(engine, df1, df2, strict: bool, cols1=None, cols2=None, suffixes=("_1", "_2"), k: int = 1, include_overlaps: bool = True,
-                         distance: bool = True, batch_rows: int = 0, limit=None, lazy: bool = False, max_batch_rows: int = 0):
-    return _arrow_stream_call(engine, "nearest", df1, df2, cols1, cols2, strict, suffixes, k, include_overlaps, distance, batch_rows, limit, lazy, max_batch_rows)
+                         distance: bool = True, batch_rows: int = 0, limit=None, lazy: bool = False, max_batch_rows: int = 0, nearest_ignore: int = 0):
+    """nearest_ignore: ONE direction mask for every df1 row (the one-call entries have no per-row orientation)."""
+    return _arrow_stream_call(engine, "nearest", df1, df2, cols1, cols2, strict, suffixes, k, include_overlaps, distance, batch_rows, limit, lazy, max_batch_rows,
+                              nearest_ignore)
 
 
 _default_engine: Optional[Engine] = None

@@ -191,9 +191,13 @@ class BuildGroups:
 
 
 def range_batches(engine, op: str, df1, df2, cols1, cols2, zero_based: bool, assemble, batch_rows: int = 8_000_000,
-                  limit: Optional[int] = None, k: int = 1, include_overlaps: bool = True, on_cols=None) -> Iterator[pa.Table]:
+                  limit: Optional[int] = None, k: int = 1, include_overlaps: bool = True, on_cols=None, nearest_ignore: int = 0,
+                  direction=None) -> Iterator[pa.Table]:
     """Generator of result tables, one per probe batch (in probe order).  ``assemble(batch_table, t2, result_dict)``
-    builds the output rows of one batch; ``limit`` bounds the total number of rows and stops the input early."""
+    builds the output rows of one batch; ``limit`` bounds the total number of rows and stops the input early.
+    nearest: ``nearest_ignore`` is the engine's direction mask; ``direction`` = (df1 column, mask of its "-" rows) splits every
+    batch by orientation into at most two sub-batches submitted to the SAME session (one df2 index in HBM) with
+    ``set_nearest_ignore`` between them -- each sub-batch yields its own result table, in df1 order."""
     assert op in OPS
     from ._engine import STREAM_COUNT, STREAM_NEAREST, STREAM_OVERLAP
     code = {"overlap": STREAM_OVERLAP, "count_overlaps": STREAM_COUNT, "nearest": STREAM_NEAREST}[op]
@@ -210,8 +214,23 @@ def range_batches(engine, op: str, df1, df2, cols1, cols2, zero_based: bool, ass
     pending = {}
     # overlap / nearest results are only used as gather indices (the assembled tables own fresh buffers); the counts column
     # would be wrapped zero-copy by pyarrow and must therefore not view the stream's recycled pinned slot
+    directed = {"nearest_ignore": int(nearest_ignore)} if (nearest_ignore or direction is not None) else {}
     stream = engine.probe_stream(build, zero_based, n_contigs, code, batch_rows, k=k, include_overlaps=include_overlaps,
-                                 copy=(op == "count_overlaps"))
+                                 copy=(op == "count_overlaps"), **directed)
+    current = int(nearest_ignore)                        # the mask the session applies to the next submit
+
+    def oriented(rb):
+        """-> the batch's (sub-batch, mask) pieces: the "+" rows under nearest_ignore, the "-" rows under the swapped mask."""
+        if direction is None:
+            return [(rb, current)]
+        name, minus_mask = direction
+        if name not in rb.schema.names:
+            raise ValueError(f"direction_col '{name}' not found in {rb.schema.names}")
+        minus = A.minus_rows(rb.column(name))
+        n_minus = int(minus.sum())
+        if n_minus == 0 or n_minus == rb.num_rows:
+            return [(rb, minus_mask if n_minus else int(nearest_ignore))]
+        return [(rb.take(pa.array(np.flatnonzero(~minus))), int(nearest_ignore)), (rb.take(pa.array(np.flatnonzero(minus))), minus_mask)]
     try:
         def deliver(res):
             nonlocal left
@@ -224,14 +243,18 @@ def range_batches(engine, op: str, df1, df2, cols1, cols2, zero_based: bool, ass
             return out
 
         n_sub = 0
-        for rb in iter_record_batches(df1, batch_rows):
-            pending[n_sub] = pa.Table.from_batches([rb])
-            n_sub += 1
-            res = stream.submit(encode_probe_batch(rb, cols1, dictionary, groups))
-            if res is not None:
-                yield deliver(res)
-                if left is not None and left <= 0:
-                    return
+        for whole in iter_record_batches(df1, batch_rows):
+            for rb, mask in oriented(whole):
+                if mask != current:
+                    stream.set_nearest_ignore(mask)
+                    current = mask
+                pending[n_sub] = pa.Table.from_batches([rb])
+                n_sub += 1
+                res = stream.submit(encode_probe_batch(rb, cols1, dictionary, groups))
+                if res is not None:
+                    yield deliver(res)
+                    if left is not None and left <= 0:
+                        return
         while True:
             res = stream.flush()
             if res is None:

@@ -218,9 +218,10 @@ class DeviceJoin:
         return out
 
     def nearest(self, probe: DeviceSide, build: DeviceSide, strict: bool, n_contigs: int, k: int = 1,
-                include_overlaps: bool = True, index=None, partition_mode: int = 0):
+                include_overlaps: bool = True, index=None, partition_mode: int = 0, nearest_ignore: int = 0):
+        """nearest_ignore: direction mask (1: leave out the rows before the probe, 2: the rows after it), one per call."""
         torch = self.torch
-        opts = make_opts(strict, n_contigs, k, include_overlaps, partition_mode=partition_mode)
+        opts = make_opts(strict, n_contigs, k, include_overlaps, partition_mode=partition_mode, nearest_ignore=nearest_ignore)
         own = index is None
         general = not (k == 1 and include_overlaps)
         ix = self.engine.index_build_dev(build.as_c(), opts, general) if own else index

@@ -229,7 +229,7 @@ def _assemble_count(t1, counts, naive_query, cols1, suffixes, on_cols=None) -> p
 
 # ---- streaming / lazy front end ----------------------------------------------------
 
-def _stream(op, df1, df2, cols1, cols2, assemble, batch_rows, limit, k=1, include_overlaps=True, zero_based=None, on_cols=None):
+def _stream(op, df1, df2, cols1, cols2, assemble, batch_rows, limit, k=1, include_overlaps=True, zero_based=None, on_cols=None, **directed):
     from . import _streaming as S
     if zero_based is None:
         zero_based = validate_coordinate_systems(df1, df2)
@@ -237,7 +237,7 @@ def _stream(op, df1, df2, cols1, cols2, assemble, batch_rows, limit, k=1, includ
     cols2 = list(DEFAULT_INTERVAL_COLUMNS if cols2 is None else cols2)
     rows = int(batch_rows) if batch_rows else _low_memory_batch_rows()
     return zero_based, S.range_batches(default_engine(), op, df1, df2, cols1, cols2, zero_based, assemble, batch_rows=rows, limit=limit,
-                                       k=k, include_overlaps=include_overlaps, on_cols=on_cols)
+                                       k=k, include_overlaps=include_overlaps, on_cols=on_cols, **directed)
 
 
 def _lazy_reader(df1, df2, zero_based, batches, assemble_empty):
@@ -289,12 +289,61 @@ def count_overlaps_batches(df1, df2, suffixes=("", "_"), cols1=None, cols2=None,
     return gen
 
 
+def _direction(df1, ignore_upstream, ignore_downstream, direction_col):
+    """-> (engine mask of the "+" rows, mask of the "-" rows or None when every row takes the same mask).  Upstream of a "+" row is
+    lower coordinates (the engine's class "left"), downstream higher ("right"); a "-" row has the two swapped, so its mask is the
+    other one's mirror -- which only differs when exactly one of the two flags is set."""
+    from ._engine import NEAREST_IGNORE_LEFT, NEAREST_IGNORE_RIGHT
+    if direction_col is not None:
+        if not isinstance(direction_col, str):
+            raise ValueError("direction_col must be the name of a df1 column")
+        names = _schema_names(df1)                            # None: a bare stream, checked when its first batch is split
+        if names is not None and direction_col not in names:
+            raise ValueError(f"direction_col '{direction_col}' not found in {names}")
+    up, down = bool(ignore_upstream), bool(ignore_downstream)
+    plus = (NEAREST_IGNORE_LEFT if up else 0) | (NEAREST_IGNORE_RIGHT if down else 0)
+    minus = (NEAREST_IGNORE_RIGHT if up else 0) | (NEAREST_IGNORE_LEFT if down else 0)
+    return plus, (minus if direction_col is not None and minus != plus else None)
+
+
+def _directed_kw(plus, minus, direction_col):
+    """Keywords of the streaming session for a directed nearest; none for the undirected call (which then is today's call)."""
+    if minus is not None:
+        return {"nearest_ignore": plus, "direction": (direction_col, minus)}
+    return {"nearest_ignore": plus} if plus else {}
+
+
+def _nearest_oriented(eng, t1, probe, build, n_contigs, zero_based, k, overlap, direction_col, plus, minus):
+    """The eager engine call(s) of a directed nearest: the engine's mask is uniform per call, so df1 rows of both orientations are
+    partitioned into two calls (the mask and its mirror) and the results scattered back to df1 row order (ivj_host_scatter)."""
+    run = lambda side, mask: eng.nearest(side, build, strict=zero_based, n_contigs=n_contigs, k=k, include_overlaps=overlap, nearest_ignore=mask)
+    if minus is None:
+        return run(probe, plus)
+    is_minus = A.minus_rows(t1.column(direction_col))
+    n_minus = int(is_minus.sum())
+    if n_minus == 0 or n_minus == len(is_minus):
+        return run(probe, minus if n_minus else plus)
+    n = len(is_minus)
+    idx, dist, nf = np.empty((n, k), np.int32), np.empty((n, k), np.int64), np.empty(n, np.int32)
+    for rows, mask in ((np.flatnonzero(~is_minus).astype(np.int32), plus), (np.flatnonzero(is_minus).astype(np.int32), minus)):
+        i, d, f = run(tuple(A.H.take(np.ascontiguousarray(c, np.int32), rows) for c in probe), mask)
+        A.H.scatter(idx, rows, np.ascontiguousarray(i, np.int32).reshape(len(rows), k))
+        A.H.scatter(dist, rows, np.ascontiguousarray(d, np.int64).reshape(len(rows), k))
+        A.H.scatter(nf, rows, f)
+    return idx, dist, nf
+
+
 def nearest_batches(df1, df2, suffixes=("_1", "_2"), cols1=None, cols2=None, k: int = 1, overlap: bool = True, distance: bool = True,
-                    batch_rows: int = 8_000_000, limit=None, as_reader: bool = False, _zero_based=None, on_cols=None):
-    """Streaming form of ``nearest`` (see ``overlap_batches``)."""
+                    batch_rows: int = 8_000_000, limit=None, as_reader: bool = False, _zero_based=None, on_cols=None, *,
+                    ignore_upstream: bool = False, ignore_downstream: bool = False, direction_col=None):
+    """Streaming form of ``nearest`` (see ``overlap_batches``).  ``ignore_upstream`` / ``ignore_downstream`` / ``direction_col``: as
+    in ``nearest``.  When df1 rows of both orientations meet in one input batch, the batch is submitted as two sub-batches (its
+    "+" rows, then its "-" rows) to the same session, and the two come out as SEPARATE result batches, each in df1 order: the
+    rows of one input batch are then not contiguous in df1 order (the reference leaves the row order unspecified)."""
+    plus, minus = _direction(df1, ignore_upstream, ignore_downstream, direction_col)
     asm = lambda bt, t2, res: _assemble_nearest(bt, t2, res["build_idx"], res["dist"], res["n_found"], suffixes, distance)
     zero_based, gen = _stream("nearest", df1, df2, cols1, cols2, asm, batch_rows, limit, k=int(k), include_overlaps=bool(overlap), zero_based=_zero_based,
-                              on_cols=on_cols)
+                              on_cols=on_cols, **_directed_kw(plus, minus, direction_col))
     if as_reader:
         kk = int(k)
         return _lazy_reader(df1, df2, zero_based, gen, lambda a, b: _assemble_nearest(a, b, np.empty((0, kk), np.int32), np.empty((0, kk), np.int64),
@@ -440,28 +489,47 @@ def nearest(
     read_options=None,
     projection_pushdown: bool = True,
     limit: Union[int, None] = None,
+    *,
+    ignore_upstream: bool = False,
+    ignore_downstream: bool = False,
+    direction_col: Union[str, None] = None,
 ):
     """Find the k closest df2 intervals of every df1 interval (reference: range_op.py:259-340;
     column order df1+suffix[0], df2+suffix[1], distance: src/operation.rs:170-197).
 
     A df1 row with no candidate on its contig yields one row with null df2 columns and a null
     distance (unpinned in the reference; tests/test_native.py:133-140 drops such rows).  ``on_cols``: the k nearest df2
-    intervals within the df1 row's group of equal (chrom, on values); a row whose group df2 lacks gets the one null row."""
+    intervals within the df1 row's group of equal (chrom, on values); a row whose group df2 lacks gets the one null row.
+
+    Directional nearest: ``ignore_upstream`` leaves out the df2 intervals that lie before the df1 interval without
+    overlapping it, ``ignore_downstream`` those that lie after it; overlapping intervals always count (unless
+    ``overlap=False``), and the answer is the k closest of what remains, distances non-negative as ever.  Without
+    ``direction_col`` every df1 row reads as "+": upstream = lower coordinates.  ``direction_col`` names a df1 column (usually
+    the strand): a row whose value is the string "-" has upstream and downstream swapped, every other value ("+", ".", null)
+    is "+"; a column df1 lacks is a ValueError.  ``on_cols=["strand"], direction_col="strand"`` is the strand-matched,
+    strand-oriented nearest.  With both flags set only overlapping intervals are reported.  On the lazy / streaming outputs
+    (``pyarrow.RecordBatchReader``, ``polars.LazyFrame``, ``limit``) the two orientations of one df1 batch may come out as
+    separate result batches, each in df1 order (see ``nearest_batches``)."""
     on_cols = _validate_overlap_input(cols1, cols2, on_cols, suffixes, output_type)
     _check_on_cols_present(on_cols, df1, df2)
+    plus, minus = _direction(df1, ignore_upstream, ignore_downstream, direction_col)
+    directed = dict(ignore_upstream=ignore_upstream, ignore_downstream=ignore_downstream, direction_col=direction_col) if (plus or minus is not None) else {}
     zero_based = validate_coordinate_systems(df1, df2)
     if output_type == "polars.LazyFrame":
         lf = _polars_lazy_result(df1, df2, zero_based, limit, nearest_batches, suffixes=suffixes, cols1=cols1, cols2=cols2, k=k, overlap=overlap,
-                                 distance=distance, batch_rows=_low_memory_batch_rows(), on_cols=on_cols)
+                                 distance=distance, batch_rows=_low_memory_batch_rows(), on_cols=on_cols, **directed)
         if lf is not None:
             return lf
     if output_type == "pyarrow.RecordBatchReader" or limit is not None:
         lazy = nearest_batches(df1, df2, suffixes, cols1, cols2, k=k, overlap=overlap, distance=distance,
-                               batch_rows=_low_memory_batch_rows(), limit=limit, as_reader=True, on_cols=on_cols)
+                               batch_rows=_low_memory_batch_rows(), limit=limit, as_reader=True, on_cols=on_cols, **directed)
         return lazy if output_type == "pyarrow.RecordBatchReader" else A.from_arrow(lazy.read_all(), output_type, zero_based)
     t1, t2, probe, build, n_contigs, keys = _prepare(df1, df2, cols1, cols2, on_cols)
-    idx, dist, nf = default_engine().nearest(probe, build, strict=zero_based, n_contigs=n_contigs, k=int(k),
-                                             include_overlaps=bool(overlap))
+    if directed:
+        idx, dist, nf = _nearest_oriented(default_engine(), t1, probe, build, n_contigs, zero_based, int(k), bool(overlap), direction_col, plus, minus)
+    else:
+        idx, dist, nf = default_engine().nearest(probe, build, strict=zero_based, n_contigs=n_contigs, k=int(k),
+                                                 include_overlaps=bool(overlap))
     return A.from_arrow(_assemble_nearest(t1, t2, idx, dist, nf, suffixes, distance, keys), output_type, zero_based)
 
 
