@@ -344,6 +344,32 @@ int ivj_merge_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_opts* opts, int64_t min
                   int32_t* contig_dev, int32_t* start_dev, int32_t* end_dev, int64_t* n_intervals_dev, int64_t* n_merged);
 int ivj_coverage_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, const ivj_opts* opts, int64_t* coverage_dev);
 
+/* ---- depth: run-length coverage blocks of one frame ------------------------------------------------------------------------------
+ * The disjoint maximal runs of positions covered by the same number (>= 1) of the frame's rows, in (contig id, start) order: the
+ * block form (chrom, start, end, coverage) of the reference's pb.depth (polars_bio/pileup_op.py:94-100), computed from an interval
+ * frame instead of an alignment file.  Strict: a row covers [start, end), blocks are half-open.  Weak: a row covers [start, end],
+ * blocks are closed (so [1,5] and [6,9] at depth 1 are the one block [1,9]).  Events at one position are netted first: neighbouring
+ * blocks differ in depth unless a gap or a contig boundary lies between them.  Zero-depth gaps are not reported (ivj_complement
+ * gives them).  Rows that cover no position (Strict start >= end, Weak start > end) and rows outside the dictionary contribute
+ * nothing; a frame with a row of start > end is indexed a second time without such rows (slower, same result).  depth is int32
+ * (bounded by the row count), at most 2 n blocks come back, and the result is bit-identical from run to run. */
+typedef struct {
+    int64_t n;
+    int32_t* contig;
+    int32_t* start;
+    int32_t* end;
+    int32_t* depth;
+} ivj_blocks;
+
+/* Host path: library-owned buffers, released by ivj_blocks_free. */
+int ivj_depth(ivj_ctx* ctx, const ivj_side* frame, const ivj_opts* opts, ivj_blocks* out);
+void ivj_blocks_free(ivj_blocks* b);
+/* Device path, the capacity protocol of ivj_merge_dev: *n_blocks always receives the total; IVJ_ECAPACITY when it exceeds
+ * `capacity`, and nothing is written then.  An index built without the end order (with_end_order bit 0) is completed on demand;
+ * a sweep-only index (bit 1) is accepted. */
+int ivj_depth_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_opts* opts, int64_t capacity, int32_t* contig_dev, int32_t* start_dev,
+                  int32_t* end_dev, int32_t* depth_dev, int64_t* n_blocks);
+
 /* ---- group ids: joins keyed on extra columns (on_cols) --------------------------------------------------------------------------
  * Every kernel partitions by one int32 id per row and ignores ids outside [0, n_contigs).  A dense GROUP id over (chrom, on_col
  * values...) passed as `contig`, with n_contigs = the number of groups, makes every operation of this header run within groups.

@@ -29,6 +29,7 @@
 #include "ixsort3.hip.h"
 #include "scan.hip.h"
 #include "group.hip.h"
+#include "depth.hip.h"
 
 using namespace ivj;
 
@@ -39,6 +40,7 @@ using namespace ivj;
 #include "host_cslice.hip.h"
 #include "host_join.hip.h"
 #include "host_sortscan.hip.h"
+#include "host_depth.hip.h"
 #include "host_stream.hip.h"
 #include "host_comm.hip.h"
 #include "host_group.hip.h"
@@ -659,6 +661,55 @@ int ivj_coverage(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, con
     HostXfer copy(ctx->stream, &ctx->xfer);
     copy.d2h(coverage, out.p, (size_t)probe->n * 8);
     HIP_TRY(copy.finish());
+    return IVJ_OK;
+} IVJ_ABI_CATCH
+
+// ---------------------------------------------------------------- depth (run-length coverage blocks)
+
+int ivj_depth_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_opts* opts, int64_t capacity, int32_t* contig_dev, int32_t* start_dev,
+                  int32_t* end_dev, int32_t* depth_dev, int64_t* n_blocks) try {
+    if (!ctx || !ix || !n_blocks) return fail(IVJ_EINVAL, "ctx, index or n_blocks is NULL");
+    IVJ_TRY(check_opts(opts));
+    if (capacity < 0) return fail(IVJ_EINVAL, "capacity < 0");
+    DeviceGuard g(ctx->device);
+    return depth_core(ctx, ix, opts, capacity, &contig_dev, &start_dev, &end_dev, &depth_dev, nullptr, n_blocks);
+} IVJ_ABI_CATCH
+
+void ivj_blocks_free(ivj_blocks* b) {
+    if (!b) return;
+    std::free(b->contig); std::free(b->start); std::free(b->end); std::free(b->depth);
+    b->contig = b->start = b->end = b->depth = nullptr; b->n = 0;
+}
+
+int ivj_depth(ivj_ctx* ctx, const ivj_side* frame, const ivj_opts* opts, ivj_blocks* out) try {
+    if (!ctx || !out) return fail(IVJ_EINVAL, "ctx or out is NULL");
+    std::memset(out, 0, sizeof(*out));
+    IVJ_TRY(check_opts(opts));
+    IVJ_TRY(check_side(frame, "frame"));
+    if (frame->n == 0) return IVJ_OK;
+    DeviceGuard g(ctx->device);
+    DevSide ds;
+    IVJ_TRY(upload_side(ctx, frame, ds));
+    IndexHolder h;
+    IVJ_TRY(index_build(ctx, &ds.s, opts, 3, &h.ix));      // sweep only (no lookup tables) + the end order
+    DevBuf own;
+    int32_t *d_contig = nullptr, *d_start = nullptr, *d_end = nullptr, *d_depth = nullptr;
+    int64_t total = 0;
+    IVJ_TRY(depth_core(ctx, h.ix, opts, -1, &d_contig, &d_start, &d_end, &d_depth, &own, &total));
+    if (total == 0) return IVJ_OK;
+    out->contig = (int32_t*)host_result_alloc((size_t)total * 4);
+    out->start = (int32_t*)host_result_alloc((size_t)total * 4);
+    out->end = (int32_t*)host_result_alloc((size_t)total * 4);
+    out->depth = (int32_t*)host_result_alloc((size_t)total * 4);
+    if (!out->contig || !out->start || !out->end || !out->depth) { ivj_blocks_free(out); return fail(IVJ_ENOMEM, "host malloc(blocks)"); }
+    HostXfer copy(ctx->stream, &ctx->xfer);
+    copy.d2h(out->contig, d_contig, (size_t)total * 4);
+    copy.d2h(out->start, d_start, (size_t)total * 4);
+    copy.d2h(out->end, d_end, (size_t)total * 4);
+    copy.d2h(out->depth, d_depth, (size_t)total * 4);
+    const hipError_t e = copy.finish();
+    if (e != hipSuccess) { ivj_blocks_free(out); return fail(IVJ_EHIP, std::string("D2H(blocks): ") + hipGetErrorString(e)); }
+    out->n = total;
     return IVJ_OK;
 } IVJ_ABI_CATCH
 

@@ -32,6 +32,7 @@ ABI_SYMBOLS = [
     "ivj_side_from_arrow", "ivj_materialize_dev", "ivj_overlap_fused_rows_dev", "ivj_take_dev", "ivj_take", "ivj_overlap_rows", "ivj_rows_free", "ivj_rows_export_arrow",
     "ivj_subtract", "ivj_complement", "ivj_pieces_free", "ivj_subtract_dev",
     "ivj_merge", "ivj_merged_free", "ivj_cluster", "ivj_coverage", "ivj_cluster_dev", "ivj_merge_dev", "ivj_coverage_dev",
+    "ivj_depth", "ivj_blocks_free", "ivj_depth_dev",
     "ivj_stream_open", "ivj_stream_submit", "ivj_stream_flush", "ivj_stream_set_nearest_ignore", "ivj_stream_close",
     "ivj_dev_alloc", "ivj_dev_free", "ivj_memcpy_h2d", "ivj_memcpy_d2h",
     "ivj_comm_unique_id", "ivj_comm_create", "ivj_comm_create_local", "ivj_comm_destroy", "ivj_comm_info",
@@ -99,6 +100,11 @@ class _Rows(C.Structure):
 class _Merged(C.Structure):
     _fields_ = [("n", C.c_int64), ("contig", C.POINTER(C.c_int32)), ("start", C.POINTER(C.c_int32)), ("end", C.POINTER(C.c_int32)),
                 ("n_intervals", C.POINTER(C.c_int64))]
+
+
+class _Blocks(C.Structure):
+    _fields_ = [("n", C.c_int64), ("contig", C.POINTER(C.c_int32)), ("start", C.POINTER(C.c_int32)), ("end", C.POINTER(C.c_int32)),
+                ("depth", C.POINTER(C.c_int32))]
 
 
 class _Pieces(C.Structure):
@@ -193,6 +199,10 @@ def load_library() -> C.CDLL:
         L.ivj_coverage.argtypes = [vp, P, P, O, vp]
         L.ivj_cluster_dev.argtypes = [vp, vp, O, C.c_int64, vp, vp, vp, C.POINTER(C.c_int64)]
         L.ivj_merge_dev.argtypes = [vp, vp, O, C.c_int64, C.c_int64, vp, vp, vp, vp, C.POINTER(C.c_int64)]
+        L.ivj_depth.argtypes = [vp, P, O, C.POINTER(_Blocks)]
+        L.ivj_blocks_free.argtypes = [C.POINTER(_Blocks)]
+        L.ivj_blocks_free.restype = None
+        L.ivj_depth_dev.argtypes = [vp, vp, O, C.c_int64, vp, vp, vp, vp, C.POINTER(C.c_int64)]
         L.ivj_coverage_dev.argtypes = [vp, vp, P, O, vp]
         L.ivj_stream_open.argtypes = [vp, P, O, C.c_int, C.c_int64, C.POINTER(vp)]
         L.ivj_stream_submit.argtypes = [vp, P, C.POINTER(_StreamResult)]
@@ -567,6 +577,22 @@ class Engine:
         finally:
             self.L.ivj_merged_free(C.byref(out))
 
+    def depth(self, frame, strict: bool, n_contigs: int):
+        """pb.depth: -> (contig id, start, end, depth) int32 arrays of the blocks of constant coverage >= 1, (contig id, start)
+        order; block bounds in the mode's own convention (Strict half-open, Weak closed)."""
+        fs, keep = _host_side(*frame)
+        o = make_opts(strict, n_contigs)
+        out = _Blocks()
+        _check(self.L, self.L.ivj_depth(self.h, C.byref(fs), C.byref(o), C.byref(out)), "ivj_depth")
+        del keep
+        try:
+            n = out.n
+            if n == 0:
+                return tuple(np.empty(0, np.int32) for _ in range(4))
+            return tuple(np.ctypeslib.as_array(getattr(out, name), shape=(n,)).copy() for name in ("contig", "start", "end", "depth"))
+        finally:
+            self.L.ivj_blocks_free(C.byref(out))
+
     def cluster(self, frame, strict: bool, n_contigs: int, min_dist: int = 0):
         """pb.cluster: -> (cluster id int64, cluster_start, cluster_end) per input row + number of clusters."""
         fs, keep = _host_side(*frame)
@@ -761,6 +787,16 @@ class Engine:
         if rc == -4:
             return n.value, False
         _check(self.L, rc, "ivj_merge_dev")
+        return n.value, True
+
+    def depth_dev(self, ix: DeviceIndex, opts: _Opts, capacity: int, contig_ptr: int, start_ptr: int, end_ptr: int, depth_ptr: int):
+        """-> (n_blocks, fits).  fits=False: nothing was written, grow the buffers to n_blocks."""
+        n = C.c_int64(0)
+        rc = self.L.ivj_depth_dev(self.h, ix.handle, C.byref(opts), int(capacity), C.c_void_p(contig_ptr or None),
+                                  C.c_void_p(start_ptr or None), C.c_void_p(end_ptr or None), C.c_void_p(depth_ptr or None), C.byref(n))
+        if rc == -4:
+            return n.value, False
+        _check(self.L, rc, "ivj_depth_dev")
         return n.value, True
 
     def subtract_dev(self, right_ix: DeviceIndex, left: _Side, opts: _Opts, capacity: int, row_ptr: int, start_ptr: int, end_ptr: int):

@@ -197,6 +197,24 @@ class DeviceJoin:
             ix.close()
         return tuple(t[:n] for t in out)
 
+    def depth(self, frame: DeviceSide, strict: bool, n_contigs: int, out=None):
+        """Blocks of constant coverage >= 1 of one frame -> (contig, start, end, depth) int32 tensors, (contig, start) order.
+        ``out``: optional preallocated 4-tuple (views of the first n_blocks elements are returned); at most 2 * frame.n
+        blocks exist."""
+        torch = self.torch
+        opts = make_opts(strict, n_contigs)
+        ix = self.engine.index_build_dev(frame.as_c(), opts, True, sweep_only=True)
+        try:
+            if out is None:
+                dev = frame.start.device
+                out = tuple(torch.empty(2 * frame.n, dtype=torch.int32, device=dev) for _ in range(4))
+            n, fits = self.engine.depth_dev(ix, opts, min(int(t.numel()) for t in out), *(t.data_ptr() for t in out))
+            if not fits:
+                raise ValueError(f"depth output buffers hold fewer than {n} blocks")
+        finally:
+            ix.close()
+        return tuple(t[:n] for t in out)
+
     def subtract(self, left: DeviceSide, right: DeviceSide, strict: bool, n_contigs: int, index=None, out=None):
         """left minus the union of right -> (left row, start, end) int32 tensors of the remaining pieces."""
         torch = self.torch

@@ -13,7 +13,7 @@ from . import range_op
 _ALIASES = {
     "overlap": (range_op.overlap, True), "nearest": (range_op.nearest, True), "count_overlaps": (range_op.count_overlaps, True),
     "coverage": (range_op.coverage, True), "subtract": (range_op.subtract, True),
-    "merge": (range_op.merge, False), "cluster": (range_op.cluster, False), "complement": (range_op.complement, False),
+    "merge": (range_op.merge, False), "depth": (range_op.depth, False), "cluster": (range_op.cluster, False), "complement": (range_op.complement, False),
 }
 
 

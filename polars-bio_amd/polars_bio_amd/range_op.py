@@ -13,6 +13,7 @@ operations -- i.e. the state after the reference's swaps in range_op.py:511
 from __future__ import annotations
 
 import logging
+import os
 from typing import Literal, Union
 
 import numpy as np
@@ -634,6 +635,57 @@ def merge(
         values = pc.take(dicts[j], pa.array(A.H.take(np.ascontiguousarray(gchrom[:, 1 + j]), c), type=pa.int32()))
         data[name] = A.cast_on_values(values, t.schema.field(name).type)
     data["n_intervals"] = pa.array(n, type=pa.int64())
+    return A.from_arrow(pa.table(data), output_type, zero_based)
+
+
+def depth(
+    df,
+    cols: Union[list, None] = ["chrom", "start", "end"],
+    on_cols: Union[list, None] = None,
+    output_type: str = "polars.LazyFrame",
+    projection_pushdown: bool = True,
+):
+    """Run-length coverage blocks of one interval frame: the disjoint maximal runs of positions covered by the same number
+    (>= 1) of rows, the bedGraph / mosdepth block form.  The reference computes these blocks from alignment files only
+    (``pb.depth``, pileup_op.py:50-118); here the reads, peaks or fragments are an interval frame.
+
+    Output: (chrom, start: Int64, end: Int64, <on_cols...>, coverage: Int64) in (chrom, start) order, block bounds in the
+    frame's own coordinate system (0-based: half-open, 1-based: closed), which is set on the result: the blocks feed straight
+    back into ``overlap`` / ``coverage``.  Zero-depth gaps are not reported (``complement`` gives them); intervals that only
+    touch do not split a block; rows that cover no position and rows with a null chrom contribute nothing.
+
+    ``on_cols``: depth per group of equal (chrom, on values), e.g. per strand; output in (chrom, on values, start) order; rows
+    with a null on-value are dropped, as rows with a null chrom are.
+
+    Two deliberate differences from the reference's file-based ``pb.depth``: the column names come from ``cols`` (there:
+    contig / pos_start / pos_end), and ``coverage`` is Int64 (there: Int16)."""
+    if isinstance(df, (str, bytes, os.PathLike)):
+        raise ValueError("depth: alignment files (BAM / SAM / CRAM) are outside this engine; an interval frame "
+                         "(polars / pandas / pyarrow, one row per aligned block) is expected")
+    on_cols = _validate_overlap_input(cols, cols, on_cols, ("_1", "_2"), output_type)
+    _check_on_cols_present(on_cols, df)
+    zero_based = validate_coordinate_system_single(df)
+    cols = list(DEFAULT_INTERVAL_COLUMNS if cols is None else cols)
+    t = A.to_arrow(df)
+    side, n_contigs, dictionary = A.encode_frame(t, cols)
+    gchrom = None
+    if on_cols:
+        # group ids over (chrom, on values) with the frame as the build side: sorted dictionaries make them ascend in that order
+        (codes,), cards, dicts, _ = A.encode_on_cols([t], on_cols)
+        empty = (np.empty(0, np.int32),) * 3
+        _, side, groups, table = A.group_sides(empty, side, n_contigs, [np.empty(0, np.int32)] * len(on_cols), codes, cards, on_cols)
+        n_contigs, gchrom = max(groups, 1), table
+    keep = side[0] >= 0                                   # rows with a null chrom (or on-value) belong to no contig
+    side = tuple(a[keep] for a in side) if not keep.all() else side
+    c, s, e, d = default_engine().depth(side, strict=zero_based, n_contigs=n_contigs)
+    c = np.ascontiguousarray(c, np.int32)
+    chrom_ids = c if gchrom is None else A.H.take(np.ascontiguousarray(gchrom[:, 0]), c)
+    data = {cols[0]: pc.cast(pc.take(dictionary, pa.array(chrom_ids, type=pa.int32())), pa.string()),
+            cols[1]: pa.array(s.astype(np.int64)), cols[2]: pa.array(e.astype(np.int64))}
+    for j, name in enumerate(on_cols or ()):
+        values = pc.take(dicts[j], pa.array(A.H.take(np.ascontiguousarray(gchrom[:, 1 + j]), c), type=pa.int32()))
+        data[name] = A.cast_on_values(values, t.schema.field(name).type)
+    data["coverage"] = pa.array(d.astype(np.int64))
     return A.from_arrow(pa.table(data), output_type, zero_based)
 
 
