@@ -315,6 +315,10 @@ int ivj_cluster(ivj_ctx* ctx, const ivj_side* frame, const ivj_opts* opts, int64
 /* pb.coverage: for every probe row the number of its positions covered by the union of the build
  * intervals of the same contig (Int64, probe order kept; [s, e) Strict, [s, e] Weak). */
 int ivj_coverage(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, int64_t* coverage);
+/* pb.mean_depth: for every probe row the positions it shares with each build interval of the same contig, summed over the
+ * build intervals (Int64, probe order kept; [s, e) Strict, [s, e] Weak) = the integral of the build side's depth over the
+ * probe row.  coverage <= bases <= count_overlaps * length.  A row that covers no position gives and receives 0. */
+int ivj_overlap_bases(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, int64_t* bases);
 
 /* pb.subtract / pb.complement (SubtractProvider / ComplementProvider, src/operation.rs:420-510): every left
  * interval minus the union of the right intervals of its contig.  Result = the remaining pieces as
@@ -343,6 +347,9 @@ int ivj_cluster_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_opts* opts, int64_t m
 int ivj_merge_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_opts* opts, int64_t min_dist, int64_t capacity,
                   int32_t* contig_dev, int32_t* start_dev, int32_t* end_dev, int64_t* n_intervals_dev, int64_t* n_merged);
 int ivj_coverage_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, const ivj_opts* opts, int64_t* coverage_dev);
+/* The position sums it reads (two uint64 arrays of n + 1 entries) are built on the index's first call and released with it;
+ * an index without the end order is completed here.  partition_mode 1 buckets the probes first; 0 and 2 run in probe order. */
+int ivj_overlap_bases_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, const ivj_opts* opts, int64_t* bases_dev);
 
 /* ---- depth: run-length coverage blocks of one frame ------------------------------------------------------------------------------
  * The disjoint maximal runs of positions covered by the same number (>= 1) of the frame's rows, in (contig id, start) order: the

@@ -263,6 +263,9 @@ struct ivj_index {
     int4* nline = nullptr;             // nearest lines (build_lines): own allocation, 128 bytes per table slot, on first use
     size_t nline_cap = 0;
     bool has_lines = false;
+    unsigned long long* psum = nullptr;  // position sums (build_position_sums): own allocation, 2 x (n + 1) uint64, on first use
+    size_t psum_stride = 0;              //   entries from the sums over the starts to the sums over the ends
+    bool has_psum = false;
     bool has_flat = false;
     bool has_rec4 = false;
     unsigned long long* spl = nullptr;   // slice path: composite key of the first row of every slice

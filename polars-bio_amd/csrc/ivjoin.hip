@@ -30,6 +30,7 @@
 #include "scan.hip.h"
 #include "group.hip.h"
 #include "depth.hip.h"
+#include "depth_sum.hip.h"
 
 using namespace ivj;
 
@@ -41,6 +42,7 @@ using namespace ivj;
 #include "host_join.hip.h"
 #include "host_sortscan.hip.h"
 #include "host_depth.hip.h"
+#include "host_depth_sum.hip.h"
 #include "host_stream.hip.h"
 #include "host_comm.hip.h"
 #include "host_group.hip.h"
@@ -246,6 +248,10 @@ void ivj_index_free(ivj_index* ix) {
             DeviceGuard g(ix->device);
             (void)hipFree(ix->nline);
         }
+    }
+    if (ix->psum) {
+        DeviceGuard g(ix->device);
+        (void)hipFree(ix->psum);
     }
     if (ix->slab) {
         if (ctx && ix->slab_cap > ctx->ix_cache_cap) {
@@ -571,6 +577,15 @@ int ivj_coverage_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, con
     return coverage_core(ctx, ix, probe_dev, opts, coverage_dev);
 } IVJ_ABI_CATCH
 
+int ivj_overlap_bases_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, const ivj_opts* opts, int64_t* bases_dev) try {
+    if (!ctx || !ix) return fail(IVJ_EINVAL, "ctx or index is NULL");
+    IVJ_TRY(check_opts(opts));
+    IVJ_TRY(check_side(probe_dev, "probe"));
+    if (probe_dev->n > 0 && !bases_dev) return fail(IVJ_EINVAL, "bases is NULL");
+    DeviceGuard g(ctx->device);
+    return depth_sum_dev(ctx, ix, probe_dev, opts, bases_dev);
+} IVJ_ABI_CATCH
+
 void ivj_merged_free(ivj_merged* m) {
     if (!m) return;
     std::free(m->contig); std::free(m->start); std::free(m->end); std::free(m->n_intervals);
@@ -660,6 +675,29 @@ int ivj_coverage(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, con
     IVJ_TRY(coverage_core(ctx, h.ix, &dp.s, opts, (int64_t*)out.p));
     HostXfer copy(ctx->stream, &ctx->xfer);
     copy.d2h(coverage, out.p, (size_t)probe->n * 8);
+    HIP_TRY(copy.finish());
+    return IVJ_OK;
+} IVJ_ABI_CATCH
+
+int ivj_overlap_bases(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, int64_t* bases) try {
+    if (!ctx) return fail(IVJ_EINVAL, "ctx is NULL");
+    IVJ_TRY(check_opts(opts));
+    IVJ_TRY(check_side(probe, "probe"));
+    IVJ_TRY(check_side(build, "build"));
+    if (probe->n == 0) return IVJ_OK;
+    if (!bases) return fail(IVJ_EINVAL, "bases is NULL");
+    DeviceGuard g(ctx->device);
+    DevSide dp, db;
+    IVJ_TRY(upload_side(ctx, build, db));
+    IVJ_TRY(upload_side(ctx, probe, dp));
+    IndexHolder h;
+    IVJ_TRY(index_build(ctx, &db.s, opts, 0, &h.ix));
+    DevBuf out;
+    hipError_t e = hipMalloc(&out.p, (size_t)probe->n * 8);
+    if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(bases): ") + hipGetErrorString(e));
+    IVJ_TRY(depth_sum_dev(ctx, h.ix, &dp.s, opts, (int64_t*)out.p));
+    HostXfer copy(ctx->stream, &ctx->xfer);
+    copy.d2h(bases, out.p, (size_t)probe->n * 8);
     HIP_TRY(copy.finish());
     return IVJ_OK;
 } IVJ_ABI_CATCH

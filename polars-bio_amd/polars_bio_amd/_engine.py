@@ -32,6 +32,7 @@ ABI_SYMBOLS = [
     "ivj_side_from_arrow", "ivj_materialize_dev", "ivj_overlap_fused_rows_dev", "ivj_take_dev", "ivj_take", "ivj_overlap_rows", "ivj_rows_free", "ivj_rows_export_arrow",
     "ivj_subtract", "ivj_complement", "ivj_pieces_free", "ivj_subtract_dev",
     "ivj_merge", "ivj_merged_free", "ivj_cluster", "ivj_coverage", "ivj_cluster_dev", "ivj_merge_dev", "ivj_coverage_dev",
+    "ivj_overlap_bases", "ivj_overlap_bases_dev",
     "ivj_depth", "ivj_blocks_free", "ivj_depth_dev",
     "ivj_stream_open", "ivj_stream_submit", "ivj_stream_flush", "ivj_stream_set_nearest_ignore", "ivj_stream_close",
     "ivj_dev_alloc", "ivj_dev_free", "ivj_memcpy_h2d", "ivj_memcpy_d2h",
@@ -204,6 +205,8 @@ def load_library() -> C.CDLL:
         L.ivj_blocks_free.restype = None
         L.ivj_depth_dev.argtypes = [vp, vp, O, C.c_int64, vp, vp, vp, vp, C.POINTER(C.c_int64)]
         L.ivj_coverage_dev.argtypes = [vp, vp, P, O, vp]
+        L.ivj_overlap_bases.argtypes = [vp, P, P, O, vp]
+        L.ivj_overlap_bases_dev.argtypes = [vp, vp, P, O, vp]
         L.ivj_stream_open.argtypes = [vp, P, O, C.c_int, C.c_int64, C.POINTER(vp)]
         L.ivj_stream_submit.argtypes = [vp, P, C.POINTER(_StreamResult)]
         L.ivj_stream_flush.argtypes = [vp, C.POINTER(_StreamResult)]
@@ -616,6 +619,16 @@ class Engine:
         del keep_p, keep_b
         return cov
 
+    def overlap_bases(self, probe, build, strict: bool, n_contigs: int, partition_mode: int = 0) -> np.ndarray:
+        """pb.mean_depth: for every probe row the positions shared with each build row of its contig, summed (int64, probe order)."""
+        ps, keep_p = _host_side(*probe)
+        bs, keep_b = _host_side(*build)
+        o = make_opts(strict, n_contigs, partition_mode=partition_mode)
+        bases = np.empty(ps.n, np.int64)
+        _check(self.L, self.L.ivj_overlap_bases(self.h, C.byref(ps), C.byref(bs), C.byref(o), bases.ctypes.data), "ivj_overlap_bases")
+        del keep_p, keep_b
+        return bases
+
     def _pieces(self, fn, name, a, b, strict, n_contigs, partition_mode=0):
         sa, keep_a = _host_side(*a)
         sb, keep_b = _host_side(*b)
@@ -812,6 +825,10 @@ class Engine:
     def coverage_dev(self, ix: DeviceIndex, probe: _Side, opts: _Opts, coverage_ptr: int):
         _check(self.L, self.L.ivj_coverage_dev(self.h, ix.handle, C.byref(probe), C.byref(opts), C.c_void_p(coverage_ptr)),
                "ivj_coverage_dev")
+
+    def overlap_bases_dev(self, ix: DeviceIndex, probe: _Side, opts: _Opts, bases_ptr: int):
+        _check(self.L, self.L.ivj_overlap_bases_dev(self.h, ix.handle, C.byref(probe), C.byref(opts), C.c_void_p(bases_ptr)),
+               "ivj_overlap_bases_dev")
 
     def count_overlaps_dev(self, ix: DeviceIndex, probe: _Side, opts: _Opts, counts_ptr: int):
         _check(self.L, self.L.ivj_count_overlaps_dev(self.h, ix.handle, C.byref(probe), C.byref(opts),

@@ -180,6 +180,22 @@ class DeviceJoin:
                 ix.close()
         return cov
 
+    def overlap_bases(self, probe: DeviceSide, build: DeviceSide, strict: bool, n_contigs: int, index=None, out=None,
+                      partition_mode: int = 0):
+        """Positions every probe row shares with each build row of its contig, summed over the build rows (the integral of the
+        build side's depth over the probe row) -> int64 tensor."""
+        torch = self.torch
+        opts = make_opts(strict, n_contigs, partition_mode=partition_mode)
+        own = index is None
+        ix = self.engine.index_build_dev(build.as_c(), opts, False) if own else index
+        try:
+            bases = out if out is not None else torch.empty(probe.n, dtype=torch.int64, device=probe.start.device)
+            self.engine.overlap_bases_dev(ix, probe.as_c(), opts, bases.data_ptr())
+        finally:
+            if own:
+                ix.close()
+        return bases
+
     def merge(self, frame: DeviceSide, strict: bool, n_contigs: int, min_dist: int = 0, out=None):
         """Merged intervals of one frame -> (contig, start, end int32, n_intervals int64) tensors.
         ``out``: optional preallocated 4-tuple (views of the first n_merged elements are returned)."""

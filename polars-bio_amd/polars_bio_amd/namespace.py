@@ -12,7 +12,7 @@ from . import range_op
 # method -> (function, takes a second frame)
 _ALIASES = {
     "overlap": (range_op.overlap, True), "nearest": (range_op.nearest, True), "count_overlaps": (range_op.count_overlaps, True),
-    "coverage": (range_op.coverage, True), "subtract": (range_op.subtract, True),
+    "coverage": (range_op.coverage, True), "mean_depth": (range_op.mean_depth, True), "subtract": (range_op.subtract, True),
     "merge": (range_op.merge, False), "depth": (range_op.depth, False), "cluster": (range_op.cluster, False), "complement": (range_op.complement, False),
 }
 

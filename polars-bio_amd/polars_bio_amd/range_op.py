@@ -27,7 +27,7 @@ from .constants import DEFAULT_INTERVAL_COLUMNS
 
 logger = logging.getLogger("polars_bio_amd")
 
-__all__ = ["overlap", "overlap_batches", "count_overlaps_batches", "nearest_batches", "nearest", "count_overlaps", "coverage", "merge", "cluster", "complement", "subtract",
+__all__ = ["overlap", "overlap_batches", "count_overlaps_batches", "nearest_batches", "nearest", "count_overlaps", "coverage", "mean_depth", "merge", "cluster", "complement", "subtract",
            "FilterOp", "RangeOp", "OverlapOutputMode"]
 
 
@@ -594,6 +594,39 @@ def coverage(
     t1, t2, probe, build, n_contigs, _keys = _prepare(df1, df2, cols1, cols2, on_cols)
     cov = default_engine().coverage(probe, build, strict=zero_based, n_contigs=n_contigs)
     return A.from_arrow(t1.append_column("coverage", pa.array(cov, type=pa.int64())), output_type, zero_based)
+
+
+def mean_depth(
+    df1,
+    df2,
+    suffixes: tuple = ("_1", "_2"),
+    on_cols: Union[list, None] = None,
+    cols1: Union[list, None] = ["chrom", "start", "end"],
+    cols2: Union[list, None] = ["chrom", "start", "end"],
+    output_type: str = "polars.LazyFrame",
+    read_options=None,
+    projection_pushdown: bool = True,
+):
+    """Total overlap and mean depth of df2 over every df1 interval: ``bases`` = the positions the df1 row shares with each df2
+    interval of its contig, summed over the df2 intervals (the integral of df2's ``depth`` over the row; ``coverage`` is the
+    integral of min(depth, 1), so coverage <= bases <= count_overlaps * length), ``mean_depth`` = bases / length of the row.
+    The per-window summary of ``mosdepth --by`` / ``bedtools coverage -mean`` for an interval frame of reads or fragments.
+
+    Output = df1 columns + ``bases`` (Int64) + ``mean_depth`` (Float64, null where the df1 row covers no position), df1 row
+    order kept.  0-based frames are half-open (intervals that only touch share nothing), 1-based frames closed.  Rows of
+    either frame that cover no position, and rows with a null chrom, share nothing.
+    ``on_cols``: only df2 intervals of the df1 row's group of equal (chrom, on values) count; a null on-value matches nothing."""
+    on_cols = _validate_overlap_input(cols1, cols2, on_cols, suffixes, output_type)
+    _check_on_cols_present(on_cols, df1, df2)
+    zero_based = validate_coordinate_systems(df1, df2)
+    t1, t2, probe, build, n_contigs, _keys = _prepare(df1, df2, cols1, cols2, on_cols)
+    bases = default_engine().overlap_bases(probe, build, strict=zero_based, n_contigs=n_contigs)
+    length = np.asarray(probe[2], np.int64) - np.asarray(probe[1], np.int64) + (0 if zero_based else 1)
+    has_positions = length > 0
+    mean = np.divide(bases.astype(np.float64), length.astype(np.float64), out=np.zeros(len(bases), np.float64), where=has_positions)
+    t = t1.append_column("bases", pa.array(bases, type=pa.int64()))
+    t = t.append_column("mean_depth", pa.array(mean, type=pa.float64(), mask=~has_positions))
+    return A.from_arrow(t, output_type, zero_based)
 
 
 def merge(
