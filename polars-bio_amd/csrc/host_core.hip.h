@@ -353,12 +353,28 @@ void t_end(ivj_ctx* ctx) {
     ctx->t_open = false;
 }
 
-#define LAUNCH(ctx, name, kernel, grid, block, ...)                                   \
+// one timed launch on the context's stream with `lds` bytes of dynamic LDS; LAUNCH: without any
+#define LAUNCH_LDS(ctx, name, kernel, grid, block, lds, ...)                          \
     do {                                                                              \
         t_begin(ctx, name);                                                           \
-        hipLaunchKernelGGL(kernel, dim3((unsigned)(grid)), dim3((unsigned)(block)), 0, (ctx)->stream, __VA_ARGS__); \
+        hipLaunchKernelGGL(kernel, dim3((unsigned)(grid)), dim3((unsigned)(block)), lds, (ctx)->stream, __VA_ARGS__); \
         t_end(ctx);                                                                   \
     } while (0)
+#define LAUNCH(ctx, name, kernel, grid, block, ...) LAUNCH_LDS(ctx, name, kernel, grid, block, 0, __VA_ARGS__)
+
+// A run-time bool becomes a template argument, once: f is a generic lambda that receives std::true_type or std::false_type by value
+// and names it where the kernel wants its bool -- with_bool(strict, [&](auto S) { LAUNCH(ctx, "x", (k_x<S>), ...); }) -- so every
+// launch and its argument list is written once.  Whatever f returns passes through: nothing, or the int status of a body that uses
+// IVJ_TRY / HIP_TRY.  Two flags: f(A, B), all four combinations are instantiated.
+template <class F>
+auto with_bool(bool b, F&& f) {
+    if (b) return f(std::true_type{});
+    return f(std::false_type{});
+}
+template <class F>
+auto with_bool(bool a, bool b, F&& f) {
+    return with_bool(a, [&](auto A) { return with_bool(b, [&](auto B) { return f(A, B); }); });
+}
 
 inline unsigned grid1d(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
 
@@ -409,8 +425,9 @@ void device_scan(ivj_ctx* ctx, const char* name, const T* in, T* out, int64_t n,
             const bool big = n >= (4ll << 20);
             const int64_t tile = (int64_t)OS_THREADS * (big ? 32 : LB_ITEMS), lt = (n + tile - 1) / tile;
             if (char* st = lb_status(ctx, lt)) {
-                if (big) LAUNCH(ctx, name, (k_scan_lb_sum<T, INCLUSIVE, 32>), lt, OS_THREADS, in, out, n, (uint32_t*)(st + align_up((size_t)lt * 8)), (unsigned long long*)st, total_out);
-                else LAUNCH(ctx, name, (k_scan_lb_sum<T, INCLUSIVE, LB_ITEMS>), lt, OS_THREADS, in, out, n, (uint32_t*)(st + align_up((size_t)lt * 8)), (unsigned long long*)st, total_out);
+                with_bool(big, [&](auto BIG) {
+                    LAUNCH(ctx, name, (k_scan_lb_sum<T, INCLUSIVE, BIG ? 32 : LB_ITEMS>), lt, OS_THREADS, in, out, n, (uint32_t*)(st + align_up((size_t)lt * 8)), (unsigned long long*)st, total_out);
+                });
                 return;
             }
         }

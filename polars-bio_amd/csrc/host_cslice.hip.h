@@ -73,21 +73,14 @@ int cs_ensure_tables(ivj_ctx* ctx, ivj_index* ix, const CsSampleArgs* sample = n
     if (sample) {
         const CsTab tab{ix->cs_spl, ix->cs_cm, ix->cs_cell};
         const size_t l2 = std::max(lds, sample->lds);
-        t_begin(ctx, "cs_bins_sample");
-        if (sample->strict)
-            hipLaunchKernelGGL((k_cs_bins_sample<true>), dim3((unsigned)g.nb + sample->sgrid), dim3(CS_THREADS), l2, ctx->stream, g.nb, (const int32_t*)ix->cs_bound, (const int32_t*)ix->b_start,
-                               (const int2*)ix->ep, (const int32_t*)ix->b_contig, (const int32_t*)ix->seg, g.R, ix->cs_bins, ix->cs_smeta, ix->flags + 1, tab, g, sample->pc, sample->ps,
-                               sample->pe, sample->n, sample->gh);
-        else
-            hipLaunchKernelGGL((k_cs_bins_sample<false>), dim3((unsigned)g.nb + sample->sgrid), dim3(CS_THREADS), l2, ctx->stream, g.nb, (const int32_t*)ix->cs_bound, (const int32_t*)ix->b_start,
-                               (const int2*)ix->ep, (const int32_t*)ix->b_contig, (const int32_t*)ix->seg, g.R, ix->cs_bins, ix->cs_smeta, ix->flags + 1, tab, g, sample->pc, sample->ps,
-                               sample->pe, sample->n, sample->gh);
-        t_end(ctx);
+        with_bool(sample->strict, [&](auto S) {
+            LAUNCH_LDS(ctx, "cs_bins_sample", (k_cs_bins_sample<S>), (unsigned)g.nb + sample->sgrid, CS_THREADS, l2, g.nb, (const int32_t*)ix->cs_bound, (const int32_t*)ix->b_start,
+                       (const int2*)ix->ep, (const int32_t*)ix->b_contig, (const int32_t*)ix->seg, g.R, ix->cs_bins, ix->cs_smeta, ix->flags + 1, tab, g, sample->pc, sample->ps,
+                       sample->pe, sample->n, sample->gh);
+        });
     } else {
-        t_begin(ctx, "cs_bins");
-        hipLaunchKernelGGL(k_cs_bins, dim3(g.nb), dim3(CS_THREADS), lds, ctx->stream, (const int32_t*)ix->cs_bound, (const int32_t*)ix->b_start, (const int2*)ix->ep,
-                           (const int32_t*)ix->b_contig, (const int32_t*)ix->seg, g.R, ix->cs_bins, ix->cs_smeta, ix->flags + 1);
-        t_end(ctx);
+        LAUNCH_LDS(ctx, "cs_bins", k_cs_bins, g.nb, CS_THREADS, lds, (const int32_t*)ix->cs_bound, (const int32_t*)ix->b_start, (const int2*)ix->ep,
+                   (const int32_t*)ix->b_contig, (const int32_t*)ix->seg, g.R, ix->cs_bins, ix->cs_smeta, ix->flags + 1);
     }
     HIP_TRY(hipGetLastError());
     // Which join kernel serves this index: the share of the build rows whose prefix max, CS_WIN rows back, still reaches past
@@ -252,10 +245,9 @@ int cs_partition(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe, const ivj_o
             const CsSampleArgs sa{strict, probe->contig, probe->start, probe->end, n, ctx->sl_gh, sgrid, hist_lds + 16};
             IVJ_TRY(cs_ensure_tables(ctx, ix, &sa));
         } else {
-            t_begin(ctx, "cs_sample");
-            if (strict) hipLaunchKernelGGL((k_cs_sample_hist<true>), dim3(sgrid), dim3(CS_THREADS), hist_lds + 16, ctx->stream, tab, g, probe->contig, probe->start, probe->end, n, ctx->sl_gh);
-            else hipLaunchKernelGGL((k_cs_sample_hist<false>), dim3(sgrid), dim3(CS_THREADS), hist_lds + 16, ctx->stream, tab, g, probe->contig, probe->start, probe->end, n, ctx->sl_gh);
-            t_end(ctx);
+            with_bool(strict, [&](auto S) {
+                LAUNCH_LDS(ctx, "cs_sample", (k_cs_sample_hist<S>), sgrid, CS_THREADS, hist_lds + 16, tab, g, probe->contig, probe->start, probe->end, n, ctx->sl_gh);
+            });
         }
         // the record format of the call (8-byte records where the sample says they fit) is decided in this kernel, on the device
         // (a context whose calls keep overflowing the 8-byte form -- a probe side with inverted or very long rows between the sampled
@@ -270,26 +262,27 @@ int cs_partition(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe, const ivj_o
         if (far_hw) HIP_TRY(hipEventRecord(ctx->cs_event, ctx->stream));
         unsigned long long* state = reinterpret_cast<unsigned long long*>(ctx->sl_meta + 4);
         if (allow8) t_begin(ctx, "cs_scatter");
-#define IVJ_CS_SCATTER_S(S, I, R8)                                                                                                      \
-    hipLaunchKernelGGL((k_cs_scatter<S, I, true, R8>), dim3(P.nchunks), dim3(CS_THREADS), P.part_lds, ctx->stream, tab, g, probe->contig, probe->start, \
-                       probe->end, probe->row_id, n, P.chunk, P.nchunks, vec, (const uint32_t*)ctx->sl_rstart, ctx->sl_rcur, state, (const int32_t*)ctx->sl_meta, rec, ctx->sl_env_ablate)
+        auto scatter = [&](auto R8) {                                         // the sampled scatter of 8-byte (R8) or 12-byte records
+            with_bool(strict, P.part_items == 8, [&](auto S, auto I8) {
+                hipLaunchKernelGGL((k_cs_scatter<S, I8 ? 8 : 4, true, R8>), dim3(P.nchunks), dim3(CS_THREADS), P.part_lds, ctx->stream, tab, g, probe->contig, probe->start,
+                                   probe->end, probe->row_id, n, P.chunk, P.nchunks, vec, (const uint32_t*)ctx->sl_rstart, ctx->sl_rcur, state, (const int32_t*)ctx->sl_meta, rec, ctx->sl_env_ablate);
+            });
+        };
         // both record forms are queued; the one the device-side format word does not name returns at once (allow8 = 0: only the 12-byte form)
         if (allow8) {
             if (P.part12) {
                 const int wide = (P.part16 && !probe->row_id) ? 16 : 12;        // 16 384-probe tiles need the rows implied (row = position)
                 const size_t ldsw = (size_t)cs_part12_lds(g.nb, g.ncells, g.n_contigs, wide).total;
-#define IVJ_CS_SCATTER_W(S, I)                                                                                                          \
-    hipLaunchKernelGGL((k_cs_scatter12k<S, I>), dim3(P.nchunks), dim3(CS_THREADS), ldsw, ctx->stream, tab, g, probe->contig, probe->start, probe->end, probe->row_id, n, \
-                       P.chunk, P.nchunks, vec, (const uint32_t*)ctx->sl_rstart, ctx->sl_rcur, state, (const int32_t*)ctx->sl_meta, rec, ctx->sl_env_ablate, ptrace)
                 unsigned long long* ptrace = nullptr;                           // IVJ_CS_PTRACE=<file> (diagnosis; tools/ptrace.py): phase stamps of the scatter's tiles
                 const char* ptrace_path = std::getenv("IVJ_CS_PTRACE");
                 if (ptrace_path && ptrace_path[0]) {
                     HIP_TRY(hipMalloc((void**)&ptrace, (size_t)P.nchunks * 64));
                     HIP_TRY(hipMemsetAsync(ptrace, 0, (size_t)P.nchunks * 64, ctx->stream));
                 }
-                if (strict) { if (wide == 16) IVJ_CS_SCATTER_W(true, 16); else IVJ_CS_SCATTER_W(true, 12); }
-                else { if (wide == 16) IVJ_CS_SCATTER_W(false, 16); else IVJ_CS_SCATTER_W(false, 12); }
-#undef IVJ_CS_SCATTER_W
+                with_bool(strict, wide == 16, [&](auto S, auto W16) {
+                    hipLaunchKernelGGL((k_cs_scatter12k<S, W16 ? 16 : 12>), dim3(P.nchunks), dim3(CS_THREADS), ldsw, ctx->stream, tab, g, probe->contig, probe->start, probe->end, probe->row_id, n,
+                                       P.chunk, P.nchunks, vec, (const uint32_t*)ctx->sl_rstart, ctx->sl_rcur, state, (const int32_t*)ctx->sl_meta, rec, ctx->sl_env_ablate, ptrace);
+                });
                 if (ptrace) {
                     std::vector<unsigned long long> h((size_t)P.nchunks * 8);
                     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -301,52 +294,39 @@ int cs_partition(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe, const ivj_o
                     }
                 }
             }
-            else if (strict) { if (P.part_items == 8) IVJ_CS_SCATTER_S(true, 8, true); else IVJ_CS_SCATTER_S(true, 4, true); }
-            else { if (P.part_items == 8) IVJ_CS_SCATTER_S(false, 8, true); else IVJ_CS_SCATTER_S(false, 4, true); }
+            else scatter(std::true_type{});
             t_end(ctx);
         }
         t_begin(ctx, allow8 ? "cs_scatter12" : "cs_scatter");
-        if (strict) { if (P.part_items == 8) IVJ_CS_SCATTER_S(true, 8, false); else IVJ_CS_SCATTER_S(true, 4, false); }
-        else { if (P.part_items == 8) IVJ_CS_SCATTER_S(false, 8, false); else IVJ_CS_SCATTER_S(false, 4, false); }
-#undef IVJ_CS_SCATTER_S
+        scatter(std::false_type{});
         t_end(ctx);
         LAUNCH(ctx, "cs_chunks", k_cs_chunks_sampled, 1, SL_THREADS, (const uint32_t*)ctx->sl_rstart, (const uint32_t*)ctx->sl_rcur, g.nb, P.jchunk, ctx->sl_bstart,
                ctx->sl_bend, ctx->sl_meta, ctx->sl_map);
         HIP_TRY(hipGetLastError());
         return IVJ_OK;
     }
-    t_begin(ctx, "cs_hist");
-    if (strict) hipLaunchKernelGGL((k_cs_hist<true>), dim3(P.nchunks), dim3(CS_THREADS), hist_lds, ctx->stream, tab, g, probe->contig, probe->end, n, P.chunk, P.nchunks, vec, ctx->sl_blk);
-    else hipLaunchKernelGGL((k_cs_hist<false>), dim3(P.nchunks), dim3(CS_THREADS), hist_lds, ctx->stream, tab, g, probe->contig, probe->end, n, P.chunk, P.nchunks, vec, ctx->sl_blk);
-    t_end(ctx);
+    with_bool(strict, [&](auto S) { LAUNCH_LDS(ctx, "cs_hist", (k_cs_hist<S>), P.nchunks, CS_THREADS, hist_lds, tab, g, probe->contig, probe->end, n, P.chunk, P.nchunks, vec, ctx->sl_blk); });
     IVJ_TRY((lb_scan_u32<SumOp, true>(ctx, "cs_scan", ctx->sl_blk, (int64_t)hist, 0u)));
     LAUNCH(ctx, "cs_chunks", k_slice_chunks, 1, SL_THREADS, (const uint32_t*)ctx->sl_blk, P.nchunks, g.nb, n, P.jchunk, ctx->sl_bstart, ctx->sl_meta, ctx->sl_map);
     if (stable) {
         const size_t lds = (size_t)cs_part_s_lds(g.nb, g.ncells, g.n_contigs).total;
         const int nbits = bits_for((uint32_t)g.nb);
-        t_begin(ctx, "cs_scatter_stable");
-        if (strict) hipLaunchKernelGGL((k_cs_scatter_stable<true>), dim3(P.nchunks), dim3(CS_THREADS), lds, ctx->stream, tab, g, nbits, probe->contig, probe->start, probe->end,
-                                       probe->row_id, n, P.chunk, P.nchunks, (const uint32_t*)ctx->sl_blk, rec);
-        else hipLaunchKernelGGL((k_cs_scatter_stable<false>), dim3(P.nchunks), dim3(CS_THREADS), lds, ctx->stream, tab, g, nbits, probe->contig, probe->start, probe->end,
-                                probe->row_id, n, P.chunk, P.nchunks, (const uint32_t*)ctx->sl_blk, rec);
-        t_end(ctx);
+        with_bool(strict, [&](auto S) {
+            LAUNCH_LDS(ctx, "cs_scatter_stable", (k_cs_scatter_stable<S>), P.nchunks, CS_THREADS, lds, tab, g, nbits, probe->contig, probe->start, probe->end,
+                       probe->row_id, n, P.chunk, P.nchunks, (const uint32_t*)ctx->sl_blk, rec);
+        });
         HIP_TRY(hipGetLastError());
         return IVJ_OK;
     }
-    t_begin(ctx, "cs_scatter");
-#define IVJ_CS_SCATTER(S, I)                                                                                                            \
-    hipLaunchKernelGGL((k_cs_scatter<S, I, false>), dim3(P.nchunks), dim3(CS_THREADS), P.part_lds, ctx->stream, tab, g, probe->contig, probe->start, \
-                       probe->end, probe->row_id, n, P.chunk, P.nchunks, vec, (const uint32_t*)ctx->sl_blk, (uint32_t*)nullptr, (unsigned long long*)nullptr, (const int32_t*)nullptr, rec, ctx->sl_env_ablate)
-    if (strict) { if (P.part_items == 8) IVJ_CS_SCATTER(true, 8); else IVJ_CS_SCATTER(true, 4); }
-    else {
-        // Weak + histogram-first: the 8192-probe tile form of this variant needs 2 spilled VGPRs (12 bytes of scratch per lane) at the
-        // kernel's 128-register ceiling; it takes the 4096-probe tiles instead (the chunks are whole tiles of either size)
-        const size_t lds4 = (size_t)cs_part_lds(g.nb, g.ncells, g.n_contigs, 4).total;
-        hipLaunchKernelGGL((k_cs_scatter<false, 4, false>), dim3(P.nchunks), dim3(CS_THREADS), lds4, ctx->stream, tab, g, probe->contig, probe->start,
-                           probe->end, probe->row_id, n, P.chunk, P.nchunks, vec, (const uint32_t*)ctx->sl_blk, (uint32_t*)nullptr, (unsigned long long*)nullptr, (const int32_t*)nullptr, rec, ctx->sl_env_ablate);
-    }
-#undef IVJ_CS_SCATTER
-    t_end(ctx);
+    // Weak + histogram-first: the 8192-probe tile form of this variant needs 2 spilled VGPRs (12 bytes of scratch per lane) at the
+    // kernel's 128-register ceiling; it takes the 4096-probe tiles instead (the chunks are whole tiles of either size) and is not instantiated
+    auto scatter = [&](auto S, auto I8) {
+        constexpr int I = I8 ? 8 : 4;
+        LAUNCH_LDS(ctx, "cs_scatter", (k_cs_scatter<S, I, false>), P.nchunks, CS_THREADS, (size_t)cs_part_lds(g.nb, g.ncells, g.n_contigs, I).total, tab, g, probe->contig, probe->start,
+                   probe->end, probe->row_id, n, P.chunk, P.nchunks, vec, (const uint32_t*)ctx->sl_blk, (uint32_t*)nullptr, (unsigned long long*)nullptr, (const int32_t*)nullptr, rec, ctx->sl_env_ablate);
+    };
+    if (strict && P.part_items == 8) scatter(std::true_type{}, std::true_type{});
+    else with_bool(strict, [&](auto S) { scatter(S, std::false_type{}); });
     HIP_TRY(hipGetLastError());
     return IVJ_OK;
 }
@@ -385,16 +365,14 @@ int cs_join_launch(ivj_ctx* ctx, ivj_index* ix, const ivj_opts* opts, const Slic
     ctx->cs_fused_hw_seq = 0;
     if (MODE == CS_FUSED && ctx->hw) { A.hw = ctx->hw_dev; A.hw_seq = ctx->cs_fused_hw_seq = ++ctx->hw_seq; }
     const unsigned grid = persist ? (unsigned)std::min(ctx->n_cus, 8 * ((P.gmax + 7) / 8)) : 8u * (unsigned)((P.gmax + 7) / 8);
-    t_begin(ctx, MODE == CS_FUSED ? "cs_join_fused" : (MODE == CS_COUNT ? "cs_join_count" : "cs_join_fill"));
-    const bool strict = opts->filter_op == IVJ_FILTER_STRICT;
-    if (ix->cs_walk) {                                     // a tail of long build rows: windows that run on walk the block maxima
-        if (strict) hipLaunchKernelGGL((k_cs_join<true, MODE>), dim3(grid), dim3(CS_THREADS), P.join_lds, ctx->stream, A);
-        else hipLaunchKernelGGL((k_cs_join<false, MODE>), dim3(grid), dim3(CS_THREADS), P.join_lds, ctx->stream, A);
-    } else {
-        if (strict) hipLaunchKernelGGL((k_cs_join_plain<true, MODE>), dim3(grid), dim3(CS_THREADS), P.join_lds, ctx->stream, A);
-        else hipLaunchKernelGGL((k_cs_join_plain<false, MODE>), dim3(grid), dim3(CS_THREADS), P.join_lds, ctx->stream, A);
-    }
-    t_end(ctx);
+    const char* name = MODE == CS_FUSED ? "cs_join_fused" : (MODE == CS_COUNT ? "cs_join_count" : "cs_join_fill");
+    with_bool(opts->filter_op == IVJ_FILTER_STRICT, [&](auto S) {
+        if (ix->cs_walk) {                                 // a tail of long build rows: windows that run on walk the block maxima
+            LAUNCH_LDS(ctx, name, (k_cs_join<S, MODE>), grid, CS_THREADS, P.join_lds, A);
+        } else {
+            LAUNCH_LDS(ctx, name, (k_cs_join_plain<S, MODE>), grid, CS_THREADS, P.join_lds, A);
+        }
+    });
     HIP_TRY(hipGetLastError());
     if (A.trace) {                                         // (synchronous on purpose: a diagnosis run)
         std::vector<unsigned long long> h((size_t)P.gmax * 6);
@@ -530,18 +508,10 @@ int cs_fill_launch(ivj_ctx* ctx, ivj_index* ix, const ivj_opts* opts, const Slic
     const size_t lds = (size_t)cs_fill_lds(g.R, wcap).total;
     const unsigned grid = 8u * (unsigned)((P.gmax + 7) / 8);
     const bool strict = opts->filter_op == IVJ_FILTER_STRICT;
-    t_begin(ctx, "cs_fill_cached");
-    if (ix->cs_walk) {
-        if (strict) hipLaunchKernelGGL((k_cs_fill<true, true, false>), dim3(grid), dim3(CS_THREADS), lds, ctx->stream, A);
-        else hipLaunchKernelGGL((k_cs_fill<false, true, false>), dim3(grid), dim3(CS_THREADS), lds, ctx->stream, A);
-    } else if (two) {
-        if (strict) hipLaunchKernelGGL((k_cs_fill<true, false, true>), dim3(grid), dim3(CS_THREADS), lds, ctx->stream, A);
-        else hipLaunchKernelGGL((k_cs_fill<false, false, true>), dim3(grid), dim3(CS_THREADS), lds, ctx->stream, A);
-    } else {
-        if (strict) hipLaunchKernelGGL((k_cs_fill<true, false, false>), dim3(grid), dim3(CS_THREADS), lds, ctx->stream, A);
-        else hipLaunchKernelGGL((k_cs_fill<false, false, false>), dim3(grid), dim3(CS_THREADS), lds, ctx->stream, A);
-    }
-    t_end(ctx);
+    auto fill = [&](auto S, auto WALK, auto TWO) { LAUNCH_LDS(ctx, "cs_fill_cached", (k_cs_fill<S, WALK, TWO>), grid, CS_THREADS, lds, A); };
+    // (`two` excludes the walking form: <S, true, true> is not instantiated)
+    if (ix->cs_walk) with_bool(strict, [&](auto S) { fill(S, std::true_type{}, std::false_type{}); });
+    else with_bool(strict, two, [&](auto S, auto TWO) { fill(S, std::false_type{}, TWO); });
     HIP_TRY(hipGetLastError());
     return IVJ_OK;
 }

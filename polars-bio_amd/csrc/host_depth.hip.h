@@ -24,15 +24,11 @@ int depth_core(ivj_ctx* ctx, ivj_index* ix, const ivj_opts* opts, int64_t capaci
     uint32_t* partials = arena_take<uint32_t>(ctx, scan_num_tiles(n_tiles) + 2);
     uint32_t* total_dev = partials + scan_num_tiles(n_tiles) + 1;
     const int32_t *bc = ix->b_contig, *bs = ix->b_start, *ee = ix->e_end;
-    if (strict) {
-        LAUNCH(ctx, "depth_partition", (k_depth_partition<true>), grid1d(n_tiles + 1, DP_THREADS), DP_THREADS, bc, bs, ee, n, n_tiles, part);
-        LAUNCH(ctx, "depth_count", (k_depth_tile<true, false>), n_tiles, DP_THREADS, bc, bs, ee, n, ix->n_contigs, (const uint32_t*)part, cnt,
+    with_bool(strict, [&](auto S) {
+        LAUNCH(ctx, "depth_partition", (k_depth_partition<S>), grid1d(n_tiles + 1, DP_THREADS), DP_THREADS, bc, bs, ee, n, n_tiles, part);
+        LAUNCH(ctx, "depth_count", (k_depth_tile<S, false>), n_tiles, DP_THREADS, bc, bs, ee, n, ix->n_contigs, (const uint32_t*)part, cnt,
                (const uint32_t*)nullptr, 0u, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr);
-    } else {
-        LAUNCH(ctx, "depth_partition", (k_depth_partition<false>), grid1d(n_tiles + 1, DP_THREADS), DP_THREADS, bc, bs, ee, n, n_tiles, part);
-        LAUNCH(ctx, "depth_count", (k_depth_tile<false, false>), n_tiles, DP_THREADS, bc, bs, ee, n, ix->n_contigs, (const uint32_t*)part, cnt,
-               (const uint32_t*)nullptr, 0u, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr);
-    }
+    });
     device_scan<uint32_t, SumOp, false>(ctx, "depth_scan", cnt, off, n_tiles, 0u, partials, total_dev);
     // the total and the index's "some row has start > end" flag come back in one wait
     ctx->h_total[0] = 0; ctx->h_total[1] = 0;
@@ -50,8 +46,7 @@ int depth_core(ivj_ctx* ctx, ivj_index* ix, const ivj_opts* opts, int64_t capaci
         hipError_t e = hipMalloc(&cols.p, 3 * col);
         if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(depth rows): ") + hipGetErrorString(e));
         int32_t* c = (int32_t*)cols.p; int32_t* s = (int32_t*)((char*)cols.p + col); int32_t* en = (int32_t*)((char*)cols.p + 2 * col);
-        if (strict) LAUNCH(ctx, "depth_sanitize", (k_depth_sanitize<true>), grid1d(n, 256), 256, bc, bs, (const int2*)ix->ep, n, ix->n_contigs, c, s, en);
-        else LAUNCH(ctx, "depth_sanitize", (k_depth_sanitize<false>), grid1d(n, 256), 256, bc, bs, (const int2*)ix->ep, n, ix->n_contigs, c, s, en);
+        with_bool(strict, [&](auto S) { LAUNCH(ctx, "depth_sanitize", (k_depth_sanitize<S>), grid1d(n, 256), 256, bc, bs, (const int2*)ix->ep, n, ix->n_contigs, c, s, en); });
         HIP_TRY(hipGetLastError());
         const ivj_side clean{c, s, en, n, nullptr};
         ivj_opts o2 = *opts;
@@ -65,21 +60,11 @@ int depth_core(ivj_ctx* ctx, ivj_index* ix, const ivj_opts* opts, int64_t capaci
     const int64_t total = (int64_t)(uint32_t)ctx->h_total[0];
     *n_blocks = total;
     if (total == 0) return IVJ_OK;
-    if (capacity < 0) {
-        const size_t col = align_up((size_t)total * 4);
-        hipError_t e = hipMalloc(&own->p, 4 * col);
-        if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(blocks): ") + hipGetErrorString(e));
-        *o_contig = (int32_t*)own->p; *o_start = (int32_t*)((char*)own->p + col);
-        *o_end = (int32_t*)((char*)own->p + 2 * col); *o_depth = (int32_t*)((char*)own->p + 3 * col);
-    } else if (total > capacity) {
-        return fail(IVJ_ECAPACITY, "depth output capacity " + std::to_string(capacity) + " < " + std::to_string(total) + " blocks");
-    } else if (!*o_contig || !*o_start || !*o_end || !*o_depth) {
-        return fail(IVJ_EINVAL, "depth output buffers are NULL");
-    }
-    if (strict) LAUNCH(ctx, "depth_fill", (k_depth_tile<true, true>), n_tiles, DP_THREADS, bc, bs, ee, n, ix->n_contigs, (const uint32_t*)part, (uint32_t*)nullptr,
-                       (const uint32_t*)off, (uint32_t)total, *o_contig, *o_start, *o_end, *o_depth);
-    else LAUNCH(ctx, "depth_fill", (k_depth_tile<false, true>), n_tiles, DP_THREADS, bc, bs, ee, n, ix->n_contigs, (const uint32_t*)part, (uint32_t*)nullptr,
-                (const uint32_t*)off, (uint32_t)total, *o_contig, *o_start, *o_end, *o_depth);
+    IVJ_TRY(place_outputs(total, capacity, {o_contig, o_start, o_end, o_depth}, own, "depth", "blocks", "depth "));
+    with_bool(strict, [&](auto S) {
+        LAUNCH(ctx, "depth_fill", (k_depth_tile<S, true>), n_tiles, DP_THREADS, bc, bs, ee, n, ix->n_contigs, (const uint32_t*)part, (uint32_t*)nullptr,
+               (const uint32_t*)off, (uint32_t)total, *o_contig, *o_start, *o_end, *o_depth);
+    });
     HIP_TRY(hipGetLastError());
     return IVJ_OK;
 }

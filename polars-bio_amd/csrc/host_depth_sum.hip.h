@@ -47,13 +47,7 @@ int depth_sum_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe, const ivj_
     long long* o_bases = (long long*)bases;
     const bool bucketed = opts->partition_mode == 1;
     if (bucketed) {
-        ivj_side plain = *probe;
-        plain.row_id = nullptr;
-        IVJ_TRY(ensure_ov(ctx, n, 1));
-        ctx->ov_n = -1;
-        ivj_opts popts = *opts; popts.partition_mode = 1;
-        IVJ_TRY(partition_probes(ctx, ix, &plain, &popts));
-        qc = ctx->pt_c; qs = ctx->pt_s; qe = ctx->pt_e;
+        IVJ_TRY(bucket_probes(ctx, ix, probe, opts, &qc, &qs, &qe));
         IVJ_TRY(arena_reserve(ctx, align_up((size_t)n * 8) + 4096));
         o_bases = arena_take<long long>(ctx, n);
     }
@@ -62,19 +56,11 @@ int depth_sum_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe, const ivj_
     const bool vec = aligned16(qc) && aligned16(qs) && aligned16(qe);
     IndexView v = view_of(ix);
     const unsigned long long *pa = ix->psum, *pe = ix->psum + ix->psum_stride;
-    const bool strict = opts->filter_op == IVJ_FILTER_STRICT;
-    if (ix->n_contigs <= CM_LDS) {
-        if (strict) LAUNCH(ctx, "depth_sum", (k_depth_sum<true, PROBE_ITEMS_LAT, true>), tiles, PROBE_THREADS, v, pa, pe, qc, qs, qe, n, vec, o_bases);
-        else LAUNCH(ctx, "depth_sum", (k_depth_sum<false, PROBE_ITEMS_LAT, true>), tiles, PROBE_THREADS, v, pa, pe, qc, qs, qe, n, vec, o_bases);
-    } else {
-        if (strict) LAUNCH(ctx, "depth_sum", (k_depth_sum<true, PROBE_ITEMS_LAT, false>), tiles, PROBE_THREADS, v, pa, pe, qc, qs, qe, n, vec, o_bases);
-        else LAUNCH(ctx, "depth_sum", (k_depth_sum<false, PROBE_ITEMS_LAT, false>), tiles, PROBE_THREADS, v, pa, pe, qc, qs, qe, n, vec, o_bases);
-    }
+    with_bool(opts->filter_op == IVJ_FILTER_STRICT, ix->n_contigs <= CM_LDS, [&](auto S, auto LM) {
+        LAUNCH(ctx, "depth_sum", (k_depth_sum<S, PROBE_ITEMS_LAT, LM>), tiles, PROBE_THREADS, v, pa, pe, qc, qs, qe, n, vec, o_bases);
+    });
     HIP_TRY(hipGetLastError());
-    if (bucketed) {
-        UnpermuteCols uc{{o_bases, nullptr, nullptr}, {bases, nullptr, nullptr}, {8, 0, 0}, 1, nullptr};
-        IVJ_TRY(unpermute(ctx, n, uc));
-    }
+    if (bucketed) IVJ_TRY(unpermute_i64(ctx, n, o_bases, bases));
     return IVJ_OK;
 }
 

@@ -90,18 +90,15 @@ int os_sort_run(ivj_ctx* ctx, OsSort& S, const int32_t* contig, const int32_t* k
         // its scan then runs over a zero histogram
         const int4* src = (p & 1) ? S.recA : S.recB;                 // pass p writes buffer p & 1 (A, B, A, ...), reads the other
         int4* dst = (p & 1) ? S.recB : S.recA;
-        if (p == 0) LAUNCH(ctx, "ix_hist", (k_os_hist<true>), S.nchunks, OS_THREADS, contig, key, src, n, S.nc, S.cbits, p, (const OsMeta*)S.meta, (int)S.chunk, S.nchunks, hist_of(p));
-        else LAUNCH(ctx, "ix_hist", (k_os_hist<false>), S.nchunks, OS_THREADS, contig, key, src, n, S.nc, S.cbits, p, (const OsMeta*)S.meta, (int)S.chunk, S.nchunks, hist_of(p));
+        with_bool(p == 0, [&](auto FIRST) {
+            LAUNCH(ctx, "ix_hist", (k_os_hist<FIRST>), S.nchunks, OS_THREADS, contig, key, src, n, S.nc, S.cbits, p, (const OsMeta*)S.meta, (int)S.chunk, S.nchunks, hist_of(p));
+        });
         LAUNCH(ctx, "ix_scan", (k_scan_lb_u32<SumOp, true>), S.hs_tiles, OS_THREADS, hist_of(p), S.hist_len, 0u, tickets + p,
                (unsigned long long*)(st_hs + (size_t)p * align_up((size_t)S.hs_tiles * 8)));
-        t_begin(ctx, "ix_pass");
-        if (p == 0)
-            hipLaunchKernelGGL((k_os_scatter<true>), dim3((unsigned)S.nchunks), dim3(OS_THREADS), pass_lds, ctx->stream, contig, key, payload,
-                               row_id, src, dst, n, S.nc, S.cbits, p, (const OsMeta*)S.meta, (int)S.chunk, S.nchunks, (const uint32_t*)hist_of(p));
-        else
-            hipLaunchKernelGGL((k_os_scatter<false>), dim3((unsigned)S.nchunks), dim3(OS_THREADS), pass_lds, ctx->stream, contig, key, payload,
-                               row_id, src, dst, n, S.nc, S.cbits, p, (const OsMeta*)S.meta, (int)S.chunk, S.nchunks, (const uint32_t*)hist_of(p));
-        t_end(ctx);
+        with_bool(p == 0, [&](auto FIRST) {
+            LAUNCH_LDS(ctx, "ix_pass", (k_os_scatter<FIRST>), S.nchunks, OS_THREADS, pass_lds, contig, key, payload,
+                       row_id, src, dst, n, S.nc, S.cbits, p, (const OsMeta*)S.meta, (int)S.chunk, S.nchunks, (const uint32_t*)hist_of(p));
+        });
     }
     HIP_TRY(hipGetLastError());
     return IVJ_OK;
@@ -359,12 +356,10 @@ int index_sort_v3(ivj_ctx* ctx, ivj_index* ix, const ivj_side* build, const ivj_
     const int bin_bits = cap <= 1024 ? 10 : (cap <= 2048 ? 11 : V3_MAX_BIN_BITS);
     const bool stage = ctx->env_ix_stage >= 0 ? ctx->env_ix_stage != 0 : cap <= 2048;
     const size_t local_lds = (size_t)v3_local_lds(cap, 1 << bin_bits, stage).total;
-    t_begin(ctx, "ix3_local");
-    if (stage) hipLaunchKernelGGL(k_v3_local<true>, dim3(V3_BUCKETS >> ms), dim3(OS_THREADS), local_lds, ctx->stream, (const int4*)recs, (const uint32_t*)hist, nchunks, n, nc, cap, bin_bits, ms,
-                                  meta, st_local, ix->b_start, ix->ep, ix->b_row, ix->b_contig, ix->seg, ix->flags);
-    else hipLaunchKernelGGL(k_v3_local<false>, dim3(V3_BUCKETS >> ms), dim3(OS_THREADS), local_lds, ctx->stream, (const int4*)recs, (const uint32_t*)hist, nchunks, n, nc, cap, bin_bits, ms,
-                            meta, st_local, ix->b_start, ix->ep, ix->b_row, ix->b_contig, ix->seg, ix->flags);
-    t_end(ctx);
+    with_bool(stage, [&](auto STAGE) {
+        LAUNCH_LDS(ctx, "ix3_local", k_v3_local<STAGE>, V3_BUCKETS >> ms, OS_THREADS, local_lds, (const int4*)recs, (const uint32_t*)hist, nchunks, n, nc, cap, bin_bits, ms,
+                   meta, st_local, ix->b_start, ix->ep, ix->b_row, ix->b_contig, ix->seg, ix->flags);
+    });
     HIP_TRY(hipGetLastError());
     *done = true;
     return IVJ_OK;

@@ -58,20 +58,15 @@ int partition_pass(ivj_ctx* ctx, ivj_index* ix, bool strict, const int32_t* sc, 
     }
     IndexView v = view_of(ix);
     const bool hvec = aligned16(sc) && aligned16(se);
-    if (strict) LAUNCH(ctx, "part_hist", (k_part_hist<true>), grid, PART_THREADS, v, sc, se, n, bshift, blk, ntiles, hvec);
-    else LAUNCH(ctx, "part_hist", (k_part_hist<false>), grid, PART_THREADS, v, sc, se, n, bshift, blk, ntiles, hvec);
+    with_bool(strict, [&](auto S) { LAUNCH(ctx, "part_hist", (k_part_hist<S>), grid, PART_THREADS, v, sc, se, n, bshift, blk, ntiles, hvec); });
     IVJ_TRY((lb_scan_u32<SumOp, true>(ctx, "part_scan", blk, (int64_t)hist, 0u)));
     // bucket b starts at blk[b * ntiles] (bucket-major scan); kept for the inverse permutation (k_unpermute)
     HIP_TRY(hipMemcpy2DAsync(ctx->pt_bstart, 4, blk, (size_t)ntiles * 4, 4, PART_BUCKETS, hipMemcpyDeviceToDevice, ctx->stream));
     HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(ctx->pt_bstart + PART_BUCKETS), (int)n, 1, ctx->stream));
-    t_begin(ctx, "part_scatter");
-    if (strict)
-        hipLaunchKernelGGL((k_part_scatter<true>), dim3(grid), dim3(PART_THREADS), PART_LDS_BYTES, ctx->stream, v, sc, ss, se, srow, n, bshift,
-                           (const uint32_t*)blk, ntiles, dc, ds, de, drow);
-    else
-        hipLaunchKernelGGL((k_part_scatter<false>), dim3(grid), dim3(PART_THREADS), PART_LDS_BYTES, ctx->stream, v, sc, ss, se, srow, n, bshift,
-                           (const uint32_t*)blk, ntiles, dc, ds, de, drow);
-    t_end(ctx);
+    with_bool(strict, [&](auto S) {
+        LAUNCH_LDS(ctx, "part_scatter", (k_part_scatter<S>), grid, PART_THREADS, PART_LDS_BYTES, v, sc, ss, se, srow, n, bshift,
+                   (const uint32_t*)blk, ntiles, dc, ds, de, drow);
+    });
     HIP_TRY(hipGetLastError());
     return IVJ_OK;
 }
@@ -83,6 +78,24 @@ int partition_probes(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe, const i
     while ((ix->bins_len >> bshift) > (int64_t)(PART_BUCKETS - 3)) ++bshift;
     return partition_pass(ctx, ix, strict, probe->contig, probe->start, probe->end, probe->row_id, n, bshift,
                           ctx->pt_c, ctx->pt_s, ctx->pt_e, ctx->pt_row);
+}
+
+// "Bucket the probes first" of the per-probe operations (count_overlaps, nearest, coverage, subtract, depth sums): one 256-way
+// partition of the probe columns by genomic position, so that the table gathers of the kernel that follows stay in the L2s.  WHETHER
+// to bucket is each caller's decision; this always does.  *qc, *qs, *qe receive the permuted columns and *qrow (where wanted) each
+// bucketed probe's position in the caller's columns -- a row_id column of the side is not carried.  They live in the context (pt_*)
+// until the next call that buckets; the partition uses the arena, so callers take their own scratch after it.  unpermute brings
+// bucket-order results back.
+int bucket_probes(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe, const ivj_opts* opts, const int32_t** qc, const int32_t** qs,
+                  const int32_t** qe, const int32_t** qrow = nullptr) {
+    ivj_side plain = *probe;
+    plain.row_id = nullptr;
+    IVJ_TRY(ensure_ov(ctx, probe->n, 1));
+    ctx->ov_n = -1;                                   // invalidates a pending count -> fill hand-over
+    IVJ_TRY(partition_probes(ctx, ix, &plain, opts));
+    *qc = ctx->pt_c; *qs = ctx->pt_s; *qe = ctx->pt_e;
+    if (qrow) *qrow = ctx->pt_row;
+    return IVJ_OK;
 }
 
 int overlap_count(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe, const ivj_opts* opts, int64_t* n_pairs) {
@@ -121,12 +134,9 @@ int overlap_count(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe, const ivj_
     }
     const bool vec = aligned16(qc) && aligned16(qs) && aligned16(qe);
     IndexView v = view_of(ix);
-    if (opts->filter_op == IVJ_FILTER_STRICT)
-        LAUNCH(ctx, "overlap_count", (k_overlap_count<true>), 8 * ((tiles + 7) / 8), PROBE_THREADS, v, qc, qs, qe, n, vec,
-               ctx->ov_hi, ctx->ov_cnt, tile);
-    else
-        LAUNCH(ctx, "overlap_count", (k_overlap_count<false>), 8 * ((tiles + 7) / 8), PROBE_THREADS, v, qc, qs, qe, n, vec,
-               ctx->ov_hi, ctx->ov_cnt, tile);
+    with_bool(opts->filter_op == IVJ_FILTER_STRICT, [&](auto S) {
+        LAUNCH(ctx, "overlap_count", (k_overlap_count<S>), 8 * ((tiles + 7) / 8), PROBE_THREADS, v, qc, qs, qe, n, vec, ctx->ov_hi, ctx->ov_cnt, tile);
+    });
     device_scan<long long, SumOp, false>(ctx, "tile_scan", tile, tile, tiles, 0ll, partials, tile + tiles);
     HIP_TRY(hipMemcpyAsync(ctx->h_total, tile + tiles, 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -173,17 +183,15 @@ int overlap_fill(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe, const ivj_o
     // dense results (>= 8 pairs per probe on average): windows shared out over all wavefronts
     const bool dense = ctx->ov_total >= 8 * n;
     const bool strict = opts->filter_op == IVJ_FILTER_STRICT;
-    if (dense) {
-        if (strict) LAUNCH(ctx, "overlap_fill_dense", (k_overlap_fill_dense<true, PROBE_ITEMS>), tiles, PROBE_THREADS, v, qs, n, vec, (const int32_t*)ctx->ov_hi,
-                           (const int32_t*)ctx->ov_cnt, (const long long*)ctx->ov_tile, ids, out_p, out_b);
-        else LAUNCH(ctx, "overlap_fill_dense", (k_overlap_fill_dense<false, PROBE_ITEMS>), tiles, PROBE_THREADS, v, qs, n, vec, (const int32_t*)ctx->ov_hi,
-                    (const int32_t*)ctx->ov_cnt, (const long long*)ctx->ov_tile, ids, out_p, out_b);
-    } else {
-        if (strict) LAUNCH(ctx, "overlap_fill", (k_overlap_fill<true>), 8 * ((tiles + 7) / 8), PROBE_THREADS, v, qs, n, vec, (const int32_t*)ctx->ov_hi,
-                           (const int32_t*)ctx->ov_cnt, (const long long*)ctx->ov_tile, ids, out_p, out_b);
-        else LAUNCH(ctx, "overlap_fill", (k_overlap_fill<false>), 8 * ((tiles + 7) / 8), PROBE_THREADS, v, qs, n, vec, (const int32_t*)ctx->ov_hi,
-                    (const int32_t*)ctx->ov_cnt, (const long long*)ctx->ov_tile, ids, out_p, out_b);
-    }
+    with_bool(strict, [&](auto S) {
+        if (dense) {
+            LAUNCH(ctx, "overlap_fill_dense", (k_overlap_fill_dense<S, PROBE_ITEMS>), tiles, PROBE_THREADS, v, qs, n, vec, (const int32_t*)ctx->ov_hi,
+                   (const int32_t*)ctx->ov_cnt, (const long long*)ctx->ov_tile, ids, out_p, out_b);
+        } else {
+            LAUNCH(ctx, "overlap_fill", (k_overlap_fill<S>), 8 * ((tiles + 7) / 8), PROBE_THREADS, v, qs, n, vec, (const int32_t*)ctx->ov_hi,
+                   (const int32_t*)ctx->ov_cnt, (const long long*)ctx->ov_tile, ids, out_p, out_b);
+        }
+    });
     HIP_TRY(hipGetLastError());
     return IVJ_OK;
 }
@@ -228,15 +236,13 @@ int overlap_fused(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe, const ivj_
         HIP_TRY(hipMemsetAsync(state, 0, 24, ctx->stream));
         const bool vec = aligned16(qc) && aligned16(qs) && aligned16(qe);
         IndexView v = view_of(ix);
-        if (flat) {
-            if (opts->filter_op == IVJ_FILTER_STRICT)
-                LAUNCH(ctx, "overlap_flat", (k_overlap_flat<true>), 8 * ((tiles + 7) / 8), FLAT_THREADS, v, qc, qs, qe, ids, n, vec, (long long)capacity, state, out_p, out_b, (int)rank_counts);
-            else
-                LAUNCH(ctx, "overlap_flat", (k_overlap_flat<false>), 8 * ((tiles + 7) / 8), FLAT_THREADS, v, qc, qs, qe, ids, n, vec, (long long)capacity, state, out_p, out_b, (int)rank_counts);
-        } else if (opts->filter_op == IVJ_FILTER_STRICT)
-            LAUNCH(ctx, "overlap_fused", (k_overlap_fused<true>), 8 * ((tiles + 7) / 8), PROBE_THREADS, v, qc, qs, qe, ids, n, vec, (long long)capacity, state, out_p, out_b);
-        else
-            LAUNCH(ctx, "overlap_fused", (k_overlap_fused<false>), 8 * ((tiles + 7) / 8), PROBE_THREADS, v, qc, qs, qe, ids, n, vec, (long long)capacity, state, out_p, out_b);
+        with_bool(opts->filter_op == IVJ_FILTER_STRICT, [&](auto S) {
+            if (flat) {
+                LAUNCH(ctx, "overlap_flat", (k_overlap_flat<S>), 8 * ((tiles + 7) / 8), FLAT_THREADS, v, qc, qs, qe, ids, n, vec, (long long)capacity, state, out_p, out_b, (int)rank_counts);
+            } else {
+                LAUNCH(ctx, "overlap_fused", (k_overlap_fused<S>), 8 * ((tiles + 7) / 8), PROBE_THREADS, v, qc, qs, qe, ids, n, vec, (long long)capacity, state, out_p, out_b);
+            }
+        });
         HIP_TRY(hipMemcpyAsync(ctx->h_total, state, 24, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         HIP_TRY(hipGetLastError());
@@ -255,12 +261,34 @@ struct DevBuf {                   // owning device allocation of the host-buffer
     ~DevBuf() { if (p) (void)hipFree(p); }
 };
 
+// Where the N int32 output columns of `total` (> 0) rows go.  capacity < 0: one library allocation in *own, carved into the columns
+// (host path); otherwise the caller's buffers, which must hold the total and exist.  what / noun word the messages ("subtract" /
+// "pieces", "depth" / "blocks"); cap_prefix is what goes before "output capacity".
+template <size_t N>
+int place_outputs(int64_t total, int64_t capacity, int32_t** const (&cols)[N], DevBuf* own, const char* what, const char* noun, const char* cap_prefix = "") {
+    if (capacity < 0) {
+        const size_t col = align_up((size_t)total * 4);
+        hipError_t e = hipMalloc(&own->p, N * col);
+        if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(") + noun + "): " + hipGetErrorString(e));
+        for (size_t k = 0; k < N; ++k) *cols[k] = (int32_t*)((char*)own->p + k * col);
+        return IVJ_OK;
+    }
+    if (total > capacity) return fail(IVJ_ECAPACITY, std::string(cap_prefix) + "output capacity " + std::to_string(capacity) + " < " + std::to_string(total) + " " + noun);
+    for (size_t k = 0; k < N; ++k)
+        if (!*cols[k]) return fail(IVJ_EINVAL, std::string(what) + " output buffers are NULL");
+    return IVJ_OK;
+}
+
 // per-probe results of a kernel that ran over the bucketed probes (pt_*) -> original row order
 int unpermute(ivj_ctx* ctx, int64_t n, const UnpermuteCols& cols) {
     LAUNCH(ctx, "unpermute", k_unpermute, (n + UNP_TILE - 1) / UNP_TILE, UNP_THREADS, (const int32_t*)ctx->pt_row, (const uint32_t*)ctx->pt_bstart,
            (const uint32_t*)ctx->pt_off, ctx->pt_ntiles, n, cols);
     HIP_TRY(hipGetLastError());
     return IVJ_OK;
+}
+// ... of the operations with one 64-bit result per probe (counts, coverage, base sums)
+int unpermute_i64(ivj_ctx* ctx, int64_t n, const long long* bucket_order, int64_t* out) {
+    return unpermute(ctx, n, UnpermuteCols{{bucket_order, nullptr, nullptr}, {out, nullptr, nullptr}, {8, 0, 0}, 1, nullptr});
 }
 
 // fused join + key-column materialisation (k_overlap_fused_rows); same partitioning as overlap_fused
@@ -286,10 +314,9 @@ int overlap_fused_rows(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe, const
     const bool vec = aligned16(qc) && aligned16(qs) && aligned16(qe) && aligned16(ids);
     IndexView v = view_of(ix);
     RowColumns cols{rows->probe_idx, rows->build_idx, rows->contig, rows->start_1, rows->end_1, rows->start_2, rows->end_2};
-    if (opts->filter_op == IVJ_FILTER_STRICT)
-        LAUNCH(ctx, "overlap_fused_rows", (k_overlap_fused_rows<true>), 8 * ((tiles + 7) / 8), PROBE_THREADS, v, qc, qs, qe, ids, n, vec, (long long)capacity, state, cols);
-    else
-        LAUNCH(ctx, "overlap_fused_rows", (k_overlap_fused_rows<false>), 8 * ((tiles + 7) / 8), PROBE_THREADS, v, qc, qs, qe, ids, n, vec, (long long)capacity, state, cols);
+    with_bool(opts->filter_op == IVJ_FILTER_STRICT, [&](auto S) {
+        LAUNCH(ctx, "overlap_fused_rows", (k_overlap_fused_rows<S>), 8 * ((tiles + 7) / 8), PROBE_THREADS, v, qc, qs, qe, ids, n, vec, (long long)capacity, state, cols);
+    });
     HIP_TRY(hipMemcpyAsync(ctx->h_total, state, 16, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     HIP_TRY(hipGetLastError());
@@ -319,13 +346,7 @@ int count_overlaps_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe, const
     long long* o_counts = (long long*)counts;
     const bool bucketed = opts->partition_mode == 1 && ix->n > 0 && !counts32;
     if (bucketed) {
-        ivj_side plain = *probe;
-        plain.row_id = nullptr;
-        IVJ_TRY(ensure_ov(ctx, n, 1));
-        ctx->ov_n = -1;
-        ivj_opts popts = *opts; popts.partition_mode = 1;
-        IVJ_TRY(partition_probes(ctx, ix, &plain, &popts));
-        qc = ctx->pt_c; qs = ctx->pt_s; qe = ctx->pt_e;
+        IVJ_TRY(bucket_probes(ctx, ix, probe, opts, &qc, &qs, &qe));
         IVJ_TRY(arena_reserve(ctx, align_up((size_t)n * 8) + 4096));
         o_counts = arena_take<long long>(ctx, n);
     }
@@ -333,37 +354,25 @@ int count_overlaps_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe, const
     const int64_t tiles = (n + NT - 1) / NT;
     const bool vec = aligned16(qc) && aligned16(qs) && aligned16(qe);
     IndexView v = view_of(ix);
-    const bool strict = opts->filter_op == IVJ_FILTER_STRICT;
-    if (ix->n_contigs <= CM_LDS && !ctx->env_count_nolds) {
-        if (strict) LAUNCH(ctx, "count_overlaps", (k_count_overlaps<true, PROBE_ITEMS_LAT, true>), tiles, PROBE_THREADS, v, qc, qs, qe, n, vec, o_counts, counts32, ctx->env_count_ablate);
-        else LAUNCH(ctx, "count_overlaps", (k_count_overlaps<false, PROBE_ITEMS_LAT, true>), tiles, PROBE_THREADS, v, qc, qs, qe, n, vec, o_counts, counts32, ctx->env_count_ablate);
-    } else {
-        if (strict) LAUNCH(ctx, "count_overlaps", (k_count_overlaps<true, PROBE_ITEMS_LAT, false>), tiles, PROBE_THREADS, v, qc, qs, qe, n, vec, o_counts, counts32, ctx->env_count_ablate);
-        else LAUNCH(ctx, "count_overlaps", (k_count_overlaps<false, PROBE_ITEMS_LAT, false>), tiles, PROBE_THREADS, v, qc, qs, qe, n, vec, o_counts, counts32, ctx->env_count_ablate);
-    }
+    with_bool(opts->filter_op == IVJ_FILTER_STRICT, ix->n_contigs <= CM_LDS && !ctx->env_count_nolds, [&](auto S, auto LM) {
+        LAUNCH(ctx, "count_overlaps", (k_count_overlaps<S, PROBE_ITEMS_LAT, LM>), tiles, PROBE_THREADS, v, qc, qs, qe, n, vec, o_counts, counts32, ctx->env_count_ablate);
+    });
     HIP_TRY(hipGetLastError());
-    if (bucketed) {
-        UnpermuteCols uc{{o_counts, nullptr, nullptr}, {counts, nullptr, nullptr}, {8, 0, 0}, 1, nullptr};
-        IVJ_TRY(unpermute(ctx, n, uc));
-    }
+    if (bucketed) IVJ_TRY(unpermute_i64(ctx, n, o_counts, counts));
     return IVJ_OK;
 }
 
 // One nearest kernel, instantiated for the filter op and for the direction mask (ivj_opts.nearest_ignore): the mask is a template
 // argument, so the undirected call launches the very instantiation it always did and no kernel tests the mask per probe.
 #define LAUNCH_NEAREST(ctx, name, KERNEL, PRE, grid, block, ...)                                                                        \
-    do {                                                                                                                               \
-        switch ((strict ? 4 : 0) | ign) {                                                                                              \
-        case 0: LAUNCH(ctx, name, (KERNEL<false PRE, 0>), grid, block, __VA_ARGS__); break;                                            \
-        case 1: LAUNCH(ctx, name "_noleft", (KERNEL<false PRE, 1>), grid, block, __VA_ARGS__); break;                                  \
-        case 2: LAUNCH(ctx, name "_noright", (KERNEL<false PRE, 2>), grid, block, __VA_ARGS__); break;                                 \
-        case 3: LAUNCH(ctx, name "_ovonly", (KERNEL<false PRE, 3>), grid, block, __VA_ARGS__); break;                                  \
-        case 4: LAUNCH(ctx, name, (KERNEL<true PRE, 0>), grid, block, __VA_ARGS__); break;                                             \
-        case 5: LAUNCH(ctx, name "_noleft", (KERNEL<true PRE, 1>), grid, block, __VA_ARGS__); break;                                   \
-        case 6: LAUNCH(ctx, name "_noright", (KERNEL<true PRE, 2>), grid, block, __VA_ARGS__); break;                                  \
-        default: LAUNCH(ctx, name "_ovonly", (KERNEL<true PRE, 3>), grid, block, __VA_ARGS__); break;                                  \
+    with_bool(strict, [&](auto S) {                                                                                                    \
+        switch (ign) {                                                                                                                 \
+        case 0: LAUNCH(ctx, name, (KERNEL<S PRE, 0>), grid, block, __VA_ARGS__); break;                                                \
+        case 1: LAUNCH(ctx, name "_noleft", (KERNEL<S PRE, 1>), grid, block, __VA_ARGS__); break;                                      \
+        case 2: LAUNCH(ctx, name "_noright", (KERNEL<S PRE, 2>), grid, block, __VA_ARGS__); break;                                     \
+        default: LAUNCH(ctx, name "_ovonly", (KERNEL<S PRE, 3>), grid, block, __VA_ARGS__); break;                                     \
         }                                                                                                                              \
-    } while (0)
+    })
 #define NEAREST_ITEMS , PROBE_ITEMS_LAT
 
 // The path choice (record / bucketed record / lines / general) does not look at the direction mask: a direction removes candidates
@@ -409,15 +418,7 @@ int nearest_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe, const ivj_op
         HIP_TRY(hipGetLastError());
         return IVJ_OK;
     }
-    if (want_partition(ix, n, opts) && ix->n > 0) {
-        ivj_side plain = *probe;
-        plain.row_id = nullptr;
-        IVJ_TRY(ensure_ov(ctx, n, 1));
-        ctx->ov_n = -1;
-        ivj_opts popts = *opts; popts.partition_mode = 1;
-        IVJ_TRY(partition_probes(ctx, ix, &plain, &popts));
-        qc = ctx->pt_c; qs = ctx->pt_s; qe = ctx->pt_e; qrow = ctx->pt_row;
-    }
+    if (want_partition(ix, n, opts) && ix->n > 0) IVJ_TRY(bucket_probes(ctx, ix, probe, opts, &qc, &qs, &qe, &qrow));
     IndexView v = view_of(ix);
     if (k1) {
         constexpr int NT = PROBE_THREADS * PROBE_ITEMS_LAT;

@@ -155,15 +155,10 @@ int slice_partition(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe, const iv
     const size_t hist_lds = (size_t)16 * SL_TAB_CONTIGS + (size_t)8 * P.g.nb + (size_t)4 * P.g.ncells + 4 * (P.g.nb + 1);
     const SliceTab tab{ix->sl_cm, ix->sl_cell};
     const size_t hist = (size_t)(P.g.nb + 1) * (size_t)P.nchunks;
-    t_begin(ctx, "slice_hist");
-    if (strict) {
-        hipLaunchKernelGGL((k_slice_hist<true>), dim3(P.nchunks), dim3(SL_THREADS), hist_lds, ctx->stream, (const unsigned long long*)ix->spl, tab, P.g,
-                           ix->n_contigs, probe->contig, probe->end, n, P.chunk, P.nchunks, vec, ctx->sl_blk);
-    } else {
-        hipLaunchKernelGGL((k_slice_hist<false>), dim3(P.nchunks), dim3(SL_THREADS), hist_lds, ctx->stream, (const unsigned long long*)ix->spl, tab, P.g,
-                           ix->n_contigs, probe->contig, probe->end, n, P.chunk, P.nchunks, vec, ctx->sl_blk);
-    }
-    t_end(ctx);
+    with_bool(strict, [&](auto S) {
+        LAUNCH_LDS(ctx, "slice_hist", (k_slice_hist<S>), P.nchunks, SL_THREADS, hist_lds, (const unsigned long long*)ix->spl, tab, P.g,
+                   ix->n_contigs, probe->contig, probe->end, n, P.chunk, P.nchunks, vec, ctx->sl_blk);
+    });
     IVJ_TRY((lb_scan_u32<SumOp, true>(ctx, "slice_scan", ctx->sl_blk, (int64_t)hist, 0u)));
     LAUNCH(ctx, "slice_chunks", k_slice_chunks, 1, SL_THREADS, (const uint32_t*)ctx->sl_blk, P.nchunks, P.g.nb, n, P.jchunk, ctx->sl_bstart,
            ctx->sl_meta, ctx->sl_map);
@@ -174,32 +169,25 @@ int slice_partition(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe, const iv
         const int thr = ctx->sl_env_sthreads == 512 ? 512 : 1024;
         const size_t ulds = (size_t)slice_part_u_lds(P.g.nb, P.g.ncells, thr).total;
         t_begin(ctx, "slice_scatter_u");
-#define IVJ_LAUNCH_SCATTER_U(S, T)                                                                                                     \
-        do {                                                                                                                          \
-            IVJ_TRY(set_dyn_lds(&k_slice_scatter_u<S, T>, ulds));                                                                     \
-            hipLaunchKernelGGL((k_slice_scatter_u<S, T>), dim3(P.nchunks), dim3(T), ulds, ctx->stream, (const unsigned long long*)ix->spl, tab, P.g, \
-                               ix->n_contigs, probe->contig, probe->start, probe->end, probe->row_id, n, P.chunk, P.nchunks,        \
-                               (const uint32_t*)ctx->sl_blk, ctx->sl_rec);                                                           \
-        } while (0)
-        if (strict) { if (thr == 512) IVJ_LAUNCH_SCATTER_U(true, 512); else IVJ_LAUNCH_SCATTER_U(true, 1024); }
-        else { if (thr == 512) IVJ_LAUNCH_SCATTER_U(false, 512); else IVJ_LAUNCH_SCATTER_U(false, 1024); }
-#undef IVJ_LAUNCH_SCATTER_U
+        IVJ_TRY(with_bool(strict, thr == 512, [&](auto S, auto T512) {
+            constexpr int T = T512 ? 512 : 1024;
+            IVJ_TRY(set_dyn_lds(&k_slice_scatter_u<S, T>, ulds));
+            hipLaunchKernelGGL((k_slice_scatter_u<S, T>), dim3(P.nchunks), dim3(T), ulds, ctx->stream, (const unsigned long long*)ix->spl, tab, P.g,
+                               ix->n_contigs, probe->contig, probe->start, probe->end, probe->row_id, n, P.chunk, P.nchunks,
+                               (const uint32_t*)ctx->sl_blk, ctx->sl_rec);
+            return IVJ_OK;
+        }));
         t_end(ctx);
         HIP_TRY(hipGetLastError());
         return IVJ_OK;
     }
-    if (strict) IVJ_TRY(set_dyn_lds(&k_slice_scatter<true>, P.part_lds)); else IVJ_TRY(set_dyn_lds(&k_slice_scatter<false>, P.part_lds));
-    t_begin(ctx, "slice_scatter");
-    if (strict) {
-        hipLaunchKernelGGL((k_slice_scatter<true>), dim3(P.nchunks), dim3(SL_THREADS), P.part_lds, ctx->stream, (const unsigned long long*)ix->spl, tab, P.g,
-                           ix->n_contigs, probe->contig, probe->start, probe->end, probe->row_id, n, P.chunk, P.nchunks,
-                           (const uint32_t*)ctx->sl_blk, ctx->sl_rec);
-    } else {
-        hipLaunchKernelGGL((k_slice_scatter<false>), dim3(P.nchunks), dim3(SL_THREADS), P.part_lds, ctx->stream, (const unsigned long long*)ix->spl, tab, P.g,
-                           ix->n_contigs, probe->contig, probe->start, probe->end, probe->row_id, n, P.chunk, P.nchunks,
-                           (const uint32_t*)ctx->sl_blk, ctx->sl_rec);
-    }
-    t_end(ctx);
+    IVJ_TRY(with_bool(strict, [&](auto S) {
+        IVJ_TRY(set_dyn_lds(&k_slice_scatter<S>, P.part_lds));
+        LAUNCH_LDS(ctx, "slice_scatter", (k_slice_scatter<S>), P.nchunks, SL_THREADS, P.part_lds, (const unsigned long long*)ix->spl, tab, P.g,
+                   ix->n_contigs, probe->contig, probe->start, probe->end, probe->row_id, n, P.chunk, P.nchunks,
+                   (const uint32_t*)ctx->sl_blk, ctx->sl_rec);
+        return IVJ_OK;
+    }));
     HIP_TRY(hipGetLastError());
     return IVJ_OK;
 }
@@ -217,17 +205,11 @@ int slice_join_launch_n(ivj_ctx* ctx, ivj_index* ix, const ivj_opts* opts, const
     const size_t lds = MODE == SL_COUNT ? P.join_lds_count : P.join_lds;
     const unsigned grid = 8u * (unsigned)((P.gmax + 7) / 8);
     const char* name = MODE == SL_COUNT ? "slice_join_count" : (MODE == SL_FILL ? "slice_join_fill" : "slice_join_fused");
-    if (opts->filter_op == IVJ_FILTER_STRICT) {
-        IVJ_TRY(set_dyn_lds(&k_slice_join<true, MODE, ITEMS>, lds));
-        t_begin(ctx, name);
-        hipLaunchKernelGGL((k_slice_join<true, MODE, ITEMS>), dim3(grid), dim3(SL_THREADS), lds, ctx->stream, P.g, ix->n, A);
-        t_end(ctx);
-    } else {
-        IVJ_TRY(set_dyn_lds(&k_slice_join<false, MODE, ITEMS>, lds));
-        t_begin(ctx, name);
-        hipLaunchKernelGGL((k_slice_join<false, MODE, ITEMS>), dim3(grid), dim3(SL_THREADS), lds, ctx->stream, P.g, ix->n, A);
-        t_end(ctx);
-    }
+    IVJ_TRY(with_bool(opts->filter_op == IVJ_FILTER_STRICT, [&](auto S) {
+        IVJ_TRY(set_dyn_lds(&k_slice_join<S, MODE, ITEMS>, lds));
+        LAUNCH_LDS(ctx, name, (k_slice_join<S, MODE, ITEMS>), grid, SL_THREADS, lds, P.g, ix->n, A);
+        return IVJ_OK;
+    }));
     HIP_TRY(hipGetLastError());
     return IVJ_OK;
 }

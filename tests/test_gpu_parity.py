@@ -1551,3 +1551,55 @@ def test_persistent_join_workgroups_match_the_oracle(monkeypatch):
             e.close()
         for k_ in kn:
             monkeypatch.delenv(k_)
+
+
+# ---- host launch drivers: every launch in both filter modes, folded second flags in both values ---------------------
+
+@pytest.mark.parametrize("strict", [True, False])
+def test_bucketed_table_forms_of_coverage_subtract_complement(eng, strict):
+    """partition_mode 1 sends coverage, subtract and complement through their table kernels over bucketed rows (the probe
+    bucketing shared with count_overlaps / nearest, then the inverse permutation or the rows' positions) where the default is
+    the union grid: both forms against the oracle on a few thousand rows over four contigs, with rows outside the dictionary,
+    an empty probe side, an empty build side, and the library-allocated outputs of the host entry points."""
+    rng = np.random.default_rng(2024)
+    nc = 4
+    left = random_side(rng, 5003, nc + 1, 200_000, 900)
+    right = random_side(rng, 3001, nc, 200_000, 300)
+    e0 = (np.empty(0, np.int32),) * 3
+    for l, r in ((left, right), (e0, right), (left, e0)):
+        exp = O.np_coverage_fast(O.Side(*l), O.Side(*r), strict)
+        er, es, ee = O.np_subtract(O.Side(*l), O.Side(*r), strict)
+        for pm in (1, 0):
+            got = eng.coverage(l, r, strict, nc, partition_mode=pm)
+            assert got.dtype == np.int64 and len(got) == len(exp) and (got == exp).all(), (len(l[0]), len(r[0]), pm)
+            gr, gs, ge = eng.subtract(l, r, strict, nc, partition_mode=pm)
+            assert len(gr) == len(er) and (gr == er).all() and (gs == es).all() and (ge == ee).all(), (len(l[0]), len(r[0]), pm)
+    view = (np.arange(nc, dtype=np.int32), np.zeros(nc, np.int32), np.full(nc, 200_000, np.int32))
+    ec, es, ee = O.np_complement(O.Side(*right), O.Side(*view), strict)
+    for pm in (1, 0):
+        gr, gs, ge = eng.complement(right, view, strict, nc, partition_mode=pm)
+        assert len(gr) == len(ec) and (view[0][gr] == ec).all() and (gs == es).all() and (ge == ee).all(), pm
+
+
+@pytest.mark.parametrize("knob", [{"IVJ_CS": "0", "IVJ_SLICE_SCATTER_THREADS": "512"}, {"IVJ_CS": "1", "IVJ_CS_FILL_TWO": "1"},
+                                  {"IVJ_IX_V3": "1", "IVJ_IX_STAGE": "0"}],
+                         ids=["scatter_u_512_threads", "cs_fill_two_workgroups", "v3_local_unstaged"])
+def test_tuning_knob_kernel_forms_match_the_oracle(knob, monkeypatch):
+    """The host drivers pick some kernel instantiations by a tuning knob next to the filter op: the unordered slice scatter with
+    512-thread workgroups, the cached slice fill with two workgroups per CU, the balanced index build's local sort without the
+    rows staged in LDS.  Each, Strict and Weak, through the fused pass and the count -> fill pair of the slice path."""
+    for k, v in knob.items():
+        monkeypatch.setenv(k, v)
+    e = _engine.Engine(0)
+    try:
+        probe = synth.make_side(100_000, 42, synth.PROBE_LEN, 24)
+        build = synth.make_side(30_000, 43, synth.BUILD_LEN, 24)
+        for strict in (True, False):
+            ep, eb = O.overlap_fast(O.Index(O.Side(*build), 24), O.Side(*probe), strict)
+            for sr in (64, 0):
+                p, b = _canon(*_fused_overlap(e, probe, build, strict, 24, 6, len(ep), slice_rows=sr))
+                assert (p == ep).all() and (b == eb).all(), ("fused", strict, sr)
+                p, b = _canon(*e.overlap(probe, build, strict, 24, partition_mode=6, slice_rows=sr))
+                assert len(p) == len(ep) and (p == ep).all() and (b == eb).all(), ("count -> fill", strict, sr)
+    finally:
+        e.close()
