@@ -377,6 +377,40 @@ void ivj_blocks_free(ivj_blocks* b);
 int ivj_depth_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_opts* opts, int64_t capacity, int32_t* contig_dev, int32_t* start_dev,
                   int32_t* end_dev, int32_t* depth_dev, int64_t* n_blocks);
 
+/* ---- set operations on two frames, and their stats (pb.set_intersect / set_union / set_difference / set_symmetric_difference,
+ * pb.jaccard) ------------------------------------------------------------------------------------------------------------------
+ * U(F) = the (contig, position) pairs at least one row of F covers, under the conventions of ivj_depth: Strict rows cover
+ * [start, end), Weak rows [start, end]; rows that cover nothing and rows outside the dictionary contribute nothing.  A set
+ * operation returns the MAXIMAL runs of op(U(a), U(b)) as (contig, start, end) in (contig id, start) order, bounds in the mode's
+ * own convention: two regions never touch or overlap (Strict [0,5) + [5,9) -> [0,9); Weak [1,5] + [6,9] -> [1,9]).  Both sides
+ * share the contig dictionary opts->n_contigs; an empty side is legal; at most runs(a) + runs(b) <= a.n + b.n regions come back;
+ * the result is bit-identical from run to run. */
+enum {
+    IVJ_SETOP_INTERSECTION = 0,          /* U(a) & U(b) */
+    IVJ_SETOP_UNION = 1,                 /* U(a) | U(b) */
+    IVJ_SETOP_DIFFERENCE = 2,            /* U(a) \ U(b) */
+    IVJ_SETOP_SYMMETRIC_DIFFERENCE = 3   /* the positions in exactly one of the two */
+};
+typedef struct {
+    int64_t n;
+    int32_t* contig;
+    int32_t* start;
+    int32_t* end;
+} ivj_regions;
+
+/* Host path: library-owned buffers, released by ivj_regions_free. */
+int ivj_setop(ivj_ctx* ctx, const ivj_side* a, const ivj_side* b, const ivj_opts* opts, int32_t op, ivj_regions* out);
+void ivj_regions_free(ivj_regions* r);
+/* bases[0..2] = the positions only U(a), only U(b), both cover (exact; intersection = bases[2], union = the sum of the three);
+ * *n_intersections = the regions ivj_setop(IVJ_SETOP_INTERSECTION) would return.  One walk, no regions written. */
+int ivj_set_stats(ivj_ctx* ctx, const ivj_side* a, const ivj_side* b, const ivj_opts* opts, int64_t bases[3], int64_t* n_intersections);
+/* Device paths over two indexes of ivj_index_build_dev (any with_end_order: a missing end order is completed on demand, sweep-only
+ * indexes are accepted; NULL = an empty side).  The capacity protocol of ivj_depth_dev: *n_regions always receives the total;
+ * IVJ_ECAPACITY when it exceeds `capacity`, and nothing is written then.  bases / n_intersections are HOST pointers. */
+int ivj_setop_dev(ivj_ctx* ctx, ivj_index* ix_a, ivj_index* ix_b, const ivj_opts* opts, int32_t op, int64_t capacity, int32_t* contig_dev,
+                  int32_t* start_dev, int32_t* end_dev, int64_t* n_regions);
+int ivj_set_stats_dev(ivj_ctx* ctx, ivj_index* ix_a, ivj_index* ix_b, const ivj_opts* opts, int64_t bases[3], int64_t* n_intersections);
+
 /* ---- group ids: joins keyed on extra columns (on_cols) --------------------------------------------------------------------------
  * Every kernel partitions by one int32 id per row and ignores ids outside [0, n_contigs).  A dense GROUP id over (chrom, on_col
  * values...) passed as `contig`, with n_contigs = the number of groups, makes every operation of this header run within groups.

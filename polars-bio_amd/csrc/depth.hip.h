@@ -78,7 +78,9 @@ __global__ __launch_bounds__(DP_THREADS) void k_depth_partition(const int32_t* _
 
 // One tile of the merged sequence.  FILL = false: tile_count[tile] = blocks opened in the tile.  FILL = true: the blocks are
 // written, tile_off[tile] = blocks opened before the tile, n_out = blocks in all (no store goes past it).
-template <bool STRICT, bool FILL>
+// RUNS (setop.hip.h: the union runs of a frame): only the transitions between depth 0 and depth >= 1 are boundaries -- a group
+// opens iff d_before == 0 && d_after != 0 and closes iff d_before != 0 && d_after == 0; o_depth is not written.
+template <bool STRICT, bool FILL, bool RUNS = false>
 __global__ __launch_bounds__(DP_THREADS) void k_depth_tile(const int32_t* __restrict__ b_contig, const int32_t* __restrict__ b_start,
                                                           const int32_t* __restrict__ e_end, int64_t n, int32_t n_contigs,
                                                           const uint32_t* __restrict__ part, uint32_t* __restrict__ tile_count,
@@ -146,8 +148,13 @@ __global__ __launch_bounds__(DP_THREADS) void k_depth_tile(const int32_t* __rest
             if (next != K) {
                 const int32_t da = (int32_t)((i0 + i) - (j0 + j));
                 const bool live = da != db && (uint32_t)(K >> 33) < (uint32_t)n_contigs;
-                if (live && da != 0) open_mask |= 1u << k;
-                if (live && db != 0) close_mask |= 1u << k;
+                if constexpr (RUNS) {
+                    if (live && db == 0) open_mask |= 1u << k;
+                    if (live && da == 0) close_mask |= 1u << k;
+                } else {
+                    if (live && da != 0) open_mask |= 1u << k;
+                    if (live && db != 0) close_mask |= 1u << k;
+                }
                 gk[k] = K; gd[k] = da;
                 db = da;
             }
@@ -168,7 +175,7 @@ __global__ __launch_bounds__(DP_THREADS) void k_depth_tile(const int32_t* __rest
             if ((open_mask & (1u << k)) && r < n_out) {
                 __builtin_nontemporal_store((int32_t)(gk[k] >> 33), o_contig + r);
                 __builtin_nontemporal_store(unflip((uint32_t)pos), o_start + r);
-                __builtin_nontemporal_store(gd[k], o_depth + r);
+                if constexpr (!RUNS) __builtin_nontemporal_store(gd[k], o_depth + r);
                 ++r;
             }
         }

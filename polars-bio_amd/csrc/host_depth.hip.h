@@ -8,8 +8,9 @@ namespace {
 // outputs in *own (host path), otherwise the caller's buffers; *n_blocks always receives the total, nothing is written
 // when it exceeds the capacity.  An index without the end order is completed here (build_end_order).
 // sanitized: the index holds no dictionary row with start > end (the second level of the slow path below).
+// runs: the maximal runs of depth >= 1 instead of the blocks (host_setop.hip.h); three columns, o_depth is not touched.
 int depth_core(ivj_ctx* ctx, ivj_index* ix, const ivj_opts* opts, int64_t capacity, int32_t** o_contig, int32_t** o_start, int32_t** o_end,
-               int32_t** o_depth, DevBuf* own, int64_t* n_blocks, bool sanitized = false) {
+               int32_t** o_depth, DevBuf* own, int64_t* n_blocks, bool sanitized = false, bool runs = false) {
     const int64_t n = ix->n;
     const bool strict = opts->filter_op == IVJ_FILTER_STRICT;
     *n_blocks = 0;
@@ -24,9 +25,9 @@ int depth_core(ivj_ctx* ctx, ivj_index* ix, const ivj_opts* opts, int64_t capaci
     uint32_t* partials = arena_take<uint32_t>(ctx, scan_num_tiles(n_tiles) + 2);
     uint32_t* total_dev = partials + scan_num_tiles(n_tiles) + 1;
     const int32_t *bc = ix->b_contig, *bs = ix->b_start, *ee = ix->e_end;
-    with_bool(strict, [&](auto S) {
+    with_bool(strict, runs, [&](auto S, auto R) {
         LAUNCH(ctx, "depth_partition", (k_depth_partition<S>), grid1d(n_tiles + 1, DP_THREADS), DP_THREADS, bc, bs, ee, n, n_tiles, part);
-        LAUNCH(ctx, "depth_count", (k_depth_tile<S, false>), n_tiles, DP_THREADS, bc, bs, ee, n, ix->n_contigs, (const uint32_t*)part, cnt,
+        LAUNCH(ctx, "depth_count", (k_depth_tile<S, false, R>), n_tiles, DP_THREADS, bc, bs, ee, n, ix->n_contigs, (const uint32_t*)part, cnt,
                (const uint32_t*)nullptr, 0u, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr);
     });
     device_scan<uint32_t, SumOp, false>(ctx, "depth_scan", cnt, off, n_tiles, 0u, partials, total_dev);
@@ -53,16 +54,17 @@ int depth_core(ivj_ctx* ctx, ivj_index* ix, const ivj_opts* opts, int64_t capaci
         o2.n_contigs = ix->n_contigs;
         IndexHolder h;
         IVJ_TRY(index_build(ctx, &clean, &o2, 3, &h.ix));    // sweep only + end order
-        const int rc = depth_core(ctx, h.ix, &o2, capacity, o_contig, o_start, o_end, o_depth, own, n_blocks, true);
+        const int rc = depth_core(ctx, h.ix, &o2, capacity, o_contig, o_start, o_end, o_depth, own, n_blocks, true, runs);
         HIP_TRY(hipStreamSynchronize(ctx->stream));          // the temporary index and columns are released on return
         return rc;
     }
     const int64_t total = (int64_t)(uint32_t)ctx->h_total[0];
     *n_blocks = total;
     if (total == 0) return IVJ_OK;
-    IVJ_TRY(place_outputs(total, capacity, {o_contig, o_start, o_end, o_depth}, own, "depth", "blocks", "depth "));
-    with_bool(strict, [&](auto S) {
-        LAUNCH(ctx, "depth_fill", (k_depth_tile<S, true>), n_tiles, DP_THREADS, bc, bs, ee, n, ix->n_contigs, (const uint32_t*)part, (uint32_t*)nullptr,
+    if (runs) IVJ_TRY(place_outputs(total, capacity, {o_contig, o_start, o_end}, own, "setop", "runs"));
+    else IVJ_TRY(place_outputs(total, capacity, {o_contig, o_start, o_end, o_depth}, own, "depth", "blocks", "depth "));
+    with_bool(strict, runs, [&](auto S, auto R) {
+        LAUNCH(ctx, "depth_fill", (k_depth_tile<S, true, R>), n_tiles, DP_THREADS, bc, bs, ee, n, ix->n_contigs, (const uint32_t*)part, (uint32_t*)nullptr,
                (const uint32_t*)off, (uint32_t)total, *o_contig, *o_start, *o_end, *o_depth);
     });
     HIP_TRY(hipGetLastError());

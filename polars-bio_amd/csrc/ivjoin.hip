@@ -31,6 +31,7 @@
 #include "group.hip.h"
 #include "depth.hip.h"
 #include "depth_sum.hip.h"
+#include "setop.hip.h"
 
 using namespace ivj;
 
@@ -43,6 +44,7 @@ using namespace ivj;
 #include "host_sortscan.hip.h"
 #include "host_depth.hip.h"
 #include "host_depth_sum.hip.h"
+#include "host_setop.hip.h"
 #include "host_stream.hip.h"
 #include "host_comm.hip.h"
 #include "host_group.hip.h"
@@ -749,6 +751,82 @@ int ivj_depth(ivj_ctx* ctx, const ivj_side* frame, const ivj_opts* opts, ivj_blo
     if (e != hipSuccess) { ivj_blocks_free(out); return fail(IVJ_EHIP, std::string("D2H(blocks): ") + hipGetErrorString(e)); }
     out->n = total;
     return IVJ_OK;
+} IVJ_ABI_CATCH
+
+// ---------------------------------------------------------------- set operations on two frames, and their stats
+
+int ivj_setop_dev(ivj_ctx* ctx, ivj_index* ix_a, ivj_index* ix_b, const ivj_opts* opts, int32_t op, int64_t capacity, int32_t* contig_dev,
+                  int32_t* start_dev, int32_t* end_dev, int64_t* n_regions) try {
+    if (!ctx || !n_regions) return fail(IVJ_EINVAL, "ctx or n_regions is NULL");
+    IVJ_TRY(check_opts(opts));
+    if (capacity < 0) return fail(IVJ_EINVAL, "capacity < 0");
+    DeviceGuard g(ctx->device);
+    return setop_core(ctx, ix_a, ix_b, opts, op, capacity, &contig_dev, &start_dev, &end_dev, nullptr, n_regions);
+} IVJ_ABI_CATCH
+
+int ivj_set_stats_dev(ivj_ctx* ctx, ivj_index* ix_a, ivj_index* ix_b, const ivj_opts* opts, int64_t bases[3], int64_t* n_intersections) try {
+    if (!ctx || !bases || !n_intersections) return fail(IVJ_EINVAL, "ctx, bases or n_intersections is NULL");
+    IVJ_TRY(check_opts(opts));
+    DeviceGuard g(ctx->device);
+    return set_stats_core(ctx, ix_a, ix_b, opts, bases, n_intersections);
+} IVJ_ABI_CATCH
+
+void ivj_regions_free(ivj_regions* r) {
+    if (!r) return;
+    std::free(r->contig); std::free(r->start); std::free(r->end);
+    r->contig = r->start = r->end = nullptr; r->n = 0;
+}
+
+namespace {
+// both sides of a host-path set operation: uploaded and indexed (sweep only + the end order); an empty side stays without an index
+struct SetSides {
+    DevSide da, db;
+    IndexHolder ha, hb;
+};
+int setop_sides(ivj_ctx* ctx, const ivj_side* a, const ivj_side* b, const ivj_opts* opts, SetSides& s) {
+    if (a->n > 0) { IVJ_TRY(upload_side(ctx, a, s.da)); IVJ_TRY(index_build(ctx, &s.da.s, opts, 3, &s.ha.ix)); }
+    if (b->n > 0) { IVJ_TRY(upload_side(ctx, b, s.db)); IVJ_TRY(index_build(ctx, &s.db.s, opts, 3, &s.hb.ix)); }
+    return IVJ_OK;
+}
+}  // namespace
+
+int ivj_setop(ivj_ctx* ctx, const ivj_side* a, const ivj_side* b, const ivj_opts* opts, int32_t op, ivj_regions* out) try {
+    if (!ctx || !out) return fail(IVJ_EINVAL, "ctx or out is NULL");
+    std::memset(out, 0, sizeof(*out));
+    IVJ_TRY(check_opts(opts));
+    IVJ_TRY(check_side(a, "a"));
+    IVJ_TRY(check_side(b, "b"));
+    DeviceGuard g(ctx->device);
+    SetSides s;
+    IVJ_TRY(setop_sides(ctx, a, b, opts, s));
+    DevBuf own;
+    int32_t *d_contig = nullptr, *d_start = nullptr, *d_end = nullptr;
+    int64_t total = 0;
+    IVJ_TRY(setop_core(ctx, s.ha.ix, s.hb.ix, opts, op, -1, &d_contig, &d_start, &d_end, &own, &total));
+    if (total == 0) return IVJ_OK;
+    out->contig = (int32_t*)host_result_alloc((size_t)total * 4);
+    out->start = (int32_t*)host_result_alloc((size_t)total * 4);
+    out->end = (int32_t*)host_result_alloc((size_t)total * 4);
+    if (!out->contig || !out->start || !out->end) { ivj_regions_free(out); return fail(IVJ_ENOMEM, "host malloc(regions)"); }
+    HostXfer copy(ctx->stream, &ctx->xfer);
+    copy.d2h(out->contig, d_contig, (size_t)total * 4);
+    copy.d2h(out->start, d_start, (size_t)total * 4);
+    copy.d2h(out->end, d_end, (size_t)total * 4);
+    const hipError_t e = copy.finish();
+    if (e != hipSuccess) { ivj_regions_free(out); return fail(IVJ_EHIP, std::string("D2H(regions): ") + hipGetErrorString(e)); }
+    out->n = total;
+    return IVJ_OK;
+} IVJ_ABI_CATCH
+
+int ivj_set_stats(ivj_ctx* ctx, const ivj_side* a, const ivj_side* b, const ivj_opts* opts, int64_t bases[3], int64_t* n_intersections) try {
+    if (!ctx || !bases || !n_intersections) return fail(IVJ_EINVAL, "ctx, bases or n_intersections is NULL");
+    IVJ_TRY(check_opts(opts));
+    IVJ_TRY(check_side(a, "a"));
+    IVJ_TRY(check_side(b, "b"));
+    DeviceGuard g(ctx->device);
+    SetSides s;
+    IVJ_TRY(setop_sides(ctx, a, b, opts, s));
+    return set_stats_core(ctx, s.ha.ix, s.hb.ix, opts, bases, n_intersections);
 } IVJ_ABI_CATCH
 
 // ---------------------------------------------------------------- subtract / complement

@@ -34,6 +34,7 @@ ABI_SYMBOLS = [
     "ivj_merge", "ivj_merged_free", "ivj_cluster", "ivj_coverage", "ivj_cluster_dev", "ivj_merge_dev", "ivj_coverage_dev",
     "ivj_overlap_bases", "ivj_overlap_bases_dev",
     "ivj_depth", "ivj_blocks_free", "ivj_depth_dev",
+    "ivj_setop", "ivj_regions_free", "ivj_set_stats", "ivj_setop_dev", "ivj_set_stats_dev",
     "ivj_stream_open", "ivj_stream_submit", "ivj_stream_flush", "ivj_stream_set_nearest_ignore", "ivj_stream_close",
     "ivj_dev_alloc", "ivj_dev_free", "ivj_memcpy_h2d", "ivj_memcpy_d2h",
     "ivj_comm_unique_id", "ivj_comm_create", "ivj_comm_create_local", "ivj_comm_destroy", "ivj_comm_info",
@@ -50,6 +51,11 @@ ABI_VERSION = 6            # include/ivjoin.h: IVJ_ABI_VERSION (struct layouts a
 STREAM_OVERLAP, STREAM_COUNT, STREAM_NEAREST = 0, 1, 2
 # ivj_opts.nearest_ignore: the candidate classes a nearest call leaves out (rows before / after the probe; overlapping rows always count)
 NEAREST_IGNORE_LEFT, NEAREST_IGNORE_RIGHT = 1, 2
+
+# the operations of ivj_setop / ivj_setop_dev (include/ivjoin.h: IVJ_SETOP_*)
+SETOP_INTERSECTION, SETOP_UNION, SETOP_DIFFERENCE, SETOP_SYMMETRIC_DIFFERENCE = 0, 1, 2, 3
+SETOPS = {"intersection": SETOP_INTERSECTION, "union": SETOP_UNION, "difference": SETOP_DIFFERENCE,
+          "symmetric_difference": SETOP_SYMMETRIC_DIFFERENCE}
 
 ROW_COLUMNS = ("probe_idx", "build_idx", "contig", "start_1", "end_1", "start_2", "end_2")
 
@@ -106,6 +112,10 @@ class _Merged(C.Structure):
 class _Blocks(C.Structure):
     _fields_ = [("n", C.c_int64), ("contig", C.POINTER(C.c_int32)), ("start", C.POINTER(C.c_int32)), ("end", C.POINTER(C.c_int32)),
                 ("depth", C.POINTER(C.c_int32))]
+
+
+class _Regions(C.Structure):
+    _fields_ = [("n", C.c_int64), ("contig", C.POINTER(C.c_int32)), ("start", C.POINTER(C.c_int32)), ("end", C.POINTER(C.c_int32))]
 
 
 class _Pieces(C.Structure):
@@ -204,6 +214,12 @@ def load_library() -> C.CDLL:
         L.ivj_blocks_free.argtypes = [C.POINTER(_Blocks)]
         L.ivj_blocks_free.restype = None
         L.ivj_depth_dev.argtypes = [vp, vp, O, C.c_int64, vp, vp, vp, vp, C.POINTER(C.c_int64)]
+        L.ivj_setop.argtypes = [vp, P, P, O, C.c_int32, C.POINTER(_Regions)]
+        L.ivj_regions_free.argtypes = [C.POINTER(_Regions)]
+        L.ivj_regions_free.restype = None
+        L.ivj_set_stats.argtypes = [vp, P, P, O, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.ivj_setop_dev.argtypes = [vp, vp, vp, O, C.c_int32, C.c_int64, vp, vp, vp, C.POINTER(C.c_int64)]
+        L.ivj_set_stats_dev.argtypes = [vp, vp, vp, O, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.ivj_coverage_dev.argtypes = [vp, vp, P, O, vp]
         L.ivj_overlap_bases.argtypes = [vp, P, P, O, vp]
         L.ivj_overlap_bases_dev.argtypes = [vp, vp, P, O, vp]
@@ -301,6 +317,16 @@ def _ignore_mask(mask) -> int:
     if mask < 0 or mask > (NEAREST_IGNORE_LEFT | NEAREST_IGNORE_RIGHT):
         raise ValueError(f"nearest_ignore must be 0 or a mask of NEAREST_IGNORE_LEFT (1) and NEAREST_IGNORE_RIGHT (2), got {mask}")
     return mask
+
+
+def _setop_code(op) -> int:
+    if isinstance(op, str):
+        if op not in SETOPS:
+            raise ValueError(f"unknown set operation '{op}': one of {sorted(SETOPS)}")
+        return SETOPS[op]
+    if int(op) not in SETOPS.values():
+        raise ValueError(f"unknown set operation {op}")
+    return int(op)
 
 
 def make_opts(strict: bool, n_contigs: int, k: int = 1, include_overlaps: bool = True, partition_mode: int = 0,
@@ -596,6 +622,36 @@ class Engine:
         finally:
             self.L.ivj_blocks_free(C.byref(out))
 
+    def setop(self, a, b, op, strict: bool, n_contigs: int):
+        """pb.set_intersect / set_union / set_difference / set_symmetric_difference: -> (contig id, start, end) int32 arrays of
+        the maximal runs of op(U(a), U(b)), (contig id, start) order, bounds in the mode's own convention.  ``op``: a name of
+        SETOPS or its number."""
+        sa, keep_a = _host_side(*a)
+        sb, keep_b = _host_side(*b)
+        o = make_opts(strict, n_contigs)
+        out = _Regions()
+        _check(self.L, self.L.ivj_setop(self.h, C.byref(sa), C.byref(sb), C.byref(o), _setop_code(op), C.byref(out)), "ivj_setop")
+        del keep_a, keep_b
+        try:
+            n = out.n
+            if n == 0:
+                return tuple(np.empty(0, np.int32) for _ in range(3))
+            return tuple(np.ctypeslib.as_array(getattr(out, name), shape=(n,)).copy() for name in ("contig", "start", "end"))
+        finally:
+            self.L.ivj_regions_free(C.byref(out))
+
+    def set_stats(self, a, b, strict: bool, n_contigs: int):
+        """-> (only_a, only_b, both, n_intersections): the positions only U(a), only U(b), both cover (exact ints) and the
+        number of regions of the intersection, from one walk."""
+        sa, keep_a = _host_side(*a)
+        sb, keep_b = _host_side(*b)
+        o = make_opts(strict, n_contigs)
+        bases = (C.c_int64 * 3)()
+        ni = C.c_int64(0)
+        _check(self.L, self.L.ivj_set_stats(self.h, C.byref(sa), C.byref(sb), C.byref(o), bases, C.byref(ni)), "ivj_set_stats")
+        del keep_a, keep_b
+        return int(bases[0]), int(bases[1]), int(bases[2]), int(ni.value)
+
     def cluster(self, frame, strict: bool, n_contigs: int, min_dist: int = 0):
         """pb.cluster: -> (cluster id int64, cluster_start, cluster_end) per input row + number of clusters."""
         fs, keep = _host_side(*frame)
@@ -811,6 +867,23 @@ class Engine:
             return n.value, False
         _check(self.L, rc, "ivj_depth_dev")
         return n.value, True
+
+    def setop_dev(self, ix_a: DeviceIndex, ix_b: DeviceIndex, opts: _Opts, op, capacity: int, contig_ptr: int, start_ptr: int, end_ptr: int):
+        """-> (n_regions, fits).  fits=False: nothing was written, grow the buffers to n_regions."""
+        n = C.c_int64(0)
+        rc = self.L.ivj_setop_dev(self.h, ix_a.handle, ix_b.handle, C.byref(opts), _setop_code(op), int(capacity),
+                                  C.c_void_p(contig_ptr or None), C.c_void_p(start_ptr or None), C.c_void_p(end_ptr or None), C.byref(n))
+        if rc == -4:
+            return n.value, False
+        _check(self.L, rc, "ivj_setop_dev")
+        return n.value, True
+
+    def set_stats_dev(self, ix_a: DeviceIndex, ix_b: DeviceIndex, opts: _Opts):
+        """-> (only_a, only_b, both, n_intersections)"""
+        bases = (C.c_int64 * 3)()
+        ni = C.c_int64(0)
+        _check(self.L, self.L.ivj_set_stats_dev(self.h, ix_a.handle, ix_b.handle, C.byref(opts), bases, C.byref(ni)), "ivj_set_stats_dev")
+        return int(bases[0]), int(bases[1]), int(bases[2]), int(ni.value)
 
     def subtract_dev(self, right_ix: DeviceIndex, left: _Side, opts: _Opts, capacity: int, row_ptr: int, start_ptr: int, end_ptr: int):
         """-> (n_pieces, fits)"""

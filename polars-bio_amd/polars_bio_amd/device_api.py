@@ -15,7 +15,7 @@ import torch  # noqa: F401  (must precede the dlopen of libivjoin_hip.so in this
 
 from typing import Optional, Tuple
 
-from ._engine import Engine, make_opts
+from ._engine import DeviceIndex, Engine, make_opts
 
 
 class DeviceSide:
@@ -230,6 +230,48 @@ class DeviceJoin:
         finally:
             ix.close()
         return tuple(t[:n] for t in out)
+
+    def _set_index(self, side: DeviceSide, opts):
+        """sweep-only index with the end order of one side of a set operation; an empty side is the NULL index"""
+        if side.n == 0:
+            return DeviceIndex(self.engine, None, 0)
+        return self.engine.index_build_dev(side.as_c(), opts, True, sweep_only=True)
+
+    def setop(self, a: DeviceSide, b: DeviceSide, op, strict: bool, n_contigs: int, out=None):
+        """Maximal runs of op(U(a), U(b)) -> (contig, start, end) int32 tensors, (contig, start) order.  ``op``: "intersection",
+        "union", "difference" or "symmetric_difference".  ``out``: optional preallocated 3-tuple (views of the first
+        n_regions elements are returned); at most a.n + b.n regions exist."""
+        torch = self.torch
+        opts = make_opts(strict, n_contigs)
+        ix_a = self._set_index(a, opts)
+        try:
+            ix_b = self._set_index(b, opts)
+            try:
+                if out is None:
+                    dev = a.start.device
+                    out = tuple(torch.empty(a.n + b.n, dtype=torch.int32, device=dev) for _ in range(3))
+                n, fits = self.engine.setop_dev(ix_a, ix_b, opts, op, min(int(t.numel()) for t in out), *(t.data_ptr() for t in out))
+                if not fits:
+                    raise ValueError(f"setop output buffers hold fewer than {n} regions")
+            finally:
+                ix_b.close()
+        finally:
+            ix_a.close()
+        return tuple(t[:n] for t in out)
+
+    def set_stats(self, a: DeviceSide, b: DeviceSide, strict: bool, n_contigs: int):
+        """-> (only_a, only_b, both, n_intersections) as Python ints: the positions only U(a), only U(b), both cover, and the
+        regions of the intersection, from one walk (what pb.jaccard needs)."""
+        opts = make_opts(strict, n_contigs)
+        ix_a = self._set_index(a, opts)
+        try:
+            ix_b = self._set_index(b, opts)
+            try:
+                return self.engine.set_stats_dev(ix_a, ix_b, opts)
+            finally:
+                ix_b.close()
+        finally:
+            ix_a.close()
 
     def subtract(self, left: DeviceSide, right: DeviceSide, strict: bool, n_contigs: int, index=None, out=None):
         """left minus the union of right -> (left row, start, end) int32 tensors of the remaining pieces."""

@@ -28,6 +28,7 @@ from .constants import DEFAULT_INTERVAL_COLUMNS
 logger = logging.getLogger("polars_bio_amd")
 
 __all__ = ["overlap", "overlap_batches", "count_overlaps_batches", "nearest_batches", "nearest", "count_overlaps", "coverage", "mean_depth", "merge", "cluster", "complement", "subtract",
+           "set_intersect", "set_union", "set_difference", "set_symmetric_difference", "jaccard",
            "FilterOp", "RangeOp", "OverlapOutputMode"]
 
 
@@ -720,6 +721,121 @@ def depth(
         data[name] = A.cast_on_values(values, t.schema.field(name).type)
     data["coverage"] = pa.array(d.astype(np.int64))
     return A.from_arrow(pa.table(data), output_type, zero_based)
+
+
+# ---- set operations on two frames (setop.hip.h) -------------------------------------------------------
+
+def _set_sides(df1, df2, cols1, cols2, on_cols):
+    """Both frames as sides of a set operation -> (t1, a, b, n_contigs, dictionary, group table, on_col dictionaries).
+    _prepare gives the shared chrom dictionary.  Its on_cols groups are ranks among the keys of df2 alone (a df1 row whose
+    key df2 lacks gets -1, which is right for a join and wrong for a union), so the groups are numbered here over the rows of
+    BOTH frames, the way merge / depth number the groups of their one frame."""
+    t1, t2, a, b, n_contigs, keys = _prepare(df1, df2, cols1, cols2)
+    # the shared dictionary is in first-occurrence order; the result is in (chrom, start) order, so the ids are renumbered
+    # in sorted-name order, as encode_frame numbers the one frame of merge / depth
+    dictionary = keys[4]
+    order = pc.sort_indices(dictionary).to_numpy(zero_copy_only=False).astype(np.int64)
+    if (order != np.arange(len(order))).any():
+        rank = np.empty(len(order), np.int32)
+        rank[order] = np.arange(len(order), dtype=np.int32)
+        dictionary = pc.take(dictionary, pa.array(order))
+        a, b = ((np.where(x[0] >= 0, rank[np.maximum(x[0], 0)], -1).astype(np.int32), x[1], x[2]) for x in (a, b))
+    gchrom = dicts = None
+    if on_cols:
+        for t in (t1, t2):
+            missing = [c for c in on_cols if c not in t.column_names]
+            assert not missing, f"on_cols {missing} not found in {t.column_names}"
+        (codes1, codes2), cards, dicts, _ = A.encode_on_cols([t1, t2], on_cols)
+        n1 = len(a[0])
+        both = tuple(np.concatenate([x, y]) for x, y in zip(a, b))
+        codes = [np.concatenate([c1, c2]) for c1, c2 in zip(codes1, codes2)]
+        empty = (np.empty(0, np.int32),) * 3
+        _, both, groups, table = A.group_sides(empty, both, n_contigs, [np.empty(0, np.int32)] * len(on_cols), codes, cards, on_cols)
+        a, b = (both[0][:n1], a[1], a[2]), (both[0][n1:], b[1], b[2])
+        n_contigs, gchrom = max(groups, 1), table
+
+    def known(side):                                      # rows with a null chrom (or on-value) belong to no contig
+        keep = side[0] >= 0
+        return side if keep.all() else tuple(np.ascontiguousarray(x[keep]) for x in side)
+    return t1, known(a), known(b), n_contigs, dictionary, gchrom, dicts
+
+
+def _set_operation(op, df1, df2, on_cols, cols1, cols2, output_type):
+    on_cols = _validate_overlap_input(cols1, cols2, on_cols, ("_1", "_2"), output_type)
+    _check_on_cols_present(on_cols, df1, df2)
+    zero_based = validate_coordinate_systems(df1, df2)
+    t1, a, b, n_contigs, dictionary, gchrom, dicts = _set_sides(df1, df2, cols1, cols2, on_cols)
+    cols = list(DEFAULT_INTERVAL_COLUMNS if cols1 is None else cols1)
+    c, s, e = default_engine().setop(a, b, op, strict=zero_based, n_contigs=n_contigs)
+    c = np.ascontiguousarray(c, np.int32)
+    chrom_ids = c if gchrom is None else A.H.take(np.ascontiguousarray(gchrom[:, 0]), c)
+    data = {cols[0]: pc.cast(pc.take(dictionary, pa.array(chrom_ids, type=pa.int32())), pa.string()),
+            cols[1]: pa.array(s.astype(np.int64)), cols[2]: pa.array(e.astype(np.int64))}
+    for j, name in enumerate(on_cols or ()):
+        values = pc.take(dicts[j], pa.array(A.H.take(np.ascontiguousarray(gchrom[:, 1 + j]), c), type=pa.int32()))
+        data[name] = A.cast_on_values(values, t1.schema.field(name).type)
+    return A.from_arrow(pa.table(data), output_type, zero_based)
+
+
+_SET_DOC = """{what}
+
+    A frame is read as the SET of (chrom, position) its rows cover: 0-based frames are half-open (a row covers [start, end)),
+    1-based frames closed ([start, end]); rows that cover no position and rows with a null chrom contribute nothing.  The
+    result is that set's maximal runs -- regions that touch are one region ([0,5) and [5,9) give [0,9); closed [1,5] and [6,9]
+    give [1,9]), no two output rows are adjacent or overlap.  (GenomicRanges intersect / union / setdiff, bioframe setdiff.)
+
+    Output: (chrom, start: Int64, end: Int64, <on_cols...>), named from ``cols1``, in (chrom, on values, start) order, bounds in
+    the frames' own coordinate system, which both frames must share and which is set on the result: it feeds straight back
+    into ``overlap``, ``coverage`` or another set operation.
+
+    ``on_cols``: positions match within groups of equal (chrom, on values) only, e.g. per strand; rows with a null on-value are
+    dropped, as rows with a null chrom are."""
+
+
+def set_intersect(df1, df2, on_cols: Union[list, None] = None, cols1: Union[list, None] = ["chrom", "start", "end"],
+                  cols2: Union[list, None] = ["chrom", "start", "end"], output_type: str = "polars.LazyFrame"):
+    return _set_operation("intersection", df1, df2, on_cols, cols1, cols2, output_type)
+
+
+def set_union(df1, df2, on_cols: Union[list, None] = None, cols1: Union[list, None] = ["chrom", "start", "end"],
+              cols2: Union[list, None] = ["chrom", "start", "end"], output_type: str = "polars.LazyFrame"):
+    return _set_operation("union", df1, df2, on_cols, cols1, cols2, output_type)
+
+
+def set_difference(df1, df2, on_cols: Union[list, None] = None, cols1: Union[list, None] = ["chrom", "start", "end"],
+                   cols2: Union[list, None] = ["chrom", "start", "end"], output_type: str = "polars.LazyFrame"):
+    return _set_operation("difference", df1, df2, on_cols, cols1, cols2, output_type)
+
+
+def set_symmetric_difference(df1, df2, on_cols: Union[list, None] = None, cols1: Union[list, None] = ["chrom", "start", "end"],
+                             cols2: Union[list, None] = ["chrom", "start", "end"], output_type: str = "polars.LazyFrame"):
+    return _set_operation("symmetric_difference", df1, df2, on_cols, cols1, cols2, output_type)
+
+
+set_intersect.__doc__ = _SET_DOC.format(what="The regions both frames cover: U(df1) & U(df2).")
+set_union.__doc__ = _SET_DOC.format(what="The regions at least one of the frames covers: U(df1) | U(df2).")
+set_difference.__doc__ = _SET_DOC.format(what="What df1 covers and df2 does not, as regions (``subtract`` gives fragments of df1's rows): U(df1) \\ U(df2).")
+set_symmetric_difference.__doc__ = _SET_DOC.format(what="The regions exactly one of the two frames covers.")
+
+
+def jaccard(df1, df2, on_cols: Union[list, None] = None, cols1: Union[list, None] = ["chrom", "start", "end"],
+            cols2: Union[list, None] = ["chrom", "start", "end"], output_type: str = "polars.LazyFrame"):
+    """Similarity of two interval frames as position sets, the columns of ``bedtools jaccard``: one row with ``intersection``
+    (Int64, positions both frames cover), ``union`` (Int64, positions at least one covers), ``jaccard`` (Float64,
+    intersection / union computed on the host from the two exact integers; null when the union is empty) and
+    ``n_intersections`` (Int64, the regions ``set_intersect`` would return).  One walk over both frames, no regions written.
+    Positions and conventions are those of the set operations; with ``on_cols`` positions match within groups of equal
+    (chrom, on values) only and the totals are summed over the groups."""
+    on_cols = _validate_overlap_input(cols1, cols2, on_cols, ("_1", "_2"), output_type)
+    _check_on_cols_present(on_cols, df1, df2)
+    zero_based = validate_coordinate_systems(df1, df2)
+    _t1, a, b, n_contigs, _dictionary, _gchrom, _dicts = _set_sides(df1, df2, cols1, cols2, on_cols)
+    only_a, only_b, both, n_int = default_engine().set_stats(a, b, strict=zero_based, n_contigs=n_contigs)
+    union = only_a + only_b + both
+    res = pa.table({"intersection": pa.array([both], type=pa.int64()), "union": pa.array([union], type=pa.int64()),
+                    "jaccard": pa.array([both / union if union else None], type=pa.float64()),
+                    "n_intersections": pa.array([n_int], type=pa.int64())})
+    return A.from_arrow(res, output_type, zero_based)
 
 
 def cluster(
