@@ -377,6 +377,31 @@ void ivj_blocks_free(ivj_blocks* b);
 int ivj_depth_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_opts* opts, int64_t capacity, int32_t* contig_dev, int32_t* start_dev,
                   int32_t* end_dev, int32_t* depth_dev, int64_t* n_blocks);
 
+/* pb.depth_summary: per probe row how deep the build side's pile gets under it, and how much of it is covered at least T deep (the
+ * columns of `mosdepth --thresholds` and of `bedtools map -o max` on a bedGraph).  With d(c, x) = the number of build rows of
+ * contig c that cover position x (the depth of ivj_depth, same conventions: [s, e) Strict, [s, e] Weak; rows that cover no
+ * position and rows outside the dictionary contribute nothing and, as probes, receive 0 in every column) and Q = the positions of
+ * probe row q on contig c:
+ *   max_depth[q]   = max over x in Q of d(c, x)                 (int32; 0 when Q is empty or nothing covers it)
+ *   bases_ge[k][q] = |{x in Q : d(c, x) >= thresholds[k]}|      (int64: a Weak probe [INT32_MIN, INT32_MAX] has 2^32 positions)
+ * bases_ge is COLUMN-MAJOR: n_thresholds columns of probe->n int64, column k belongs to thresholds[k], in the caller's order.
+ * Thresholds may come in any order and may repeat; each must be >= 1; n_thresholds in [0, IVJ_MAX_THRESHOLDS].  max_depth may be
+ * NULL (thresholds only); bases_ge may be NULL only when n_thresholds == 0.  IVJ_EINVAL: n_thresholds outside its range,
+ * thresholds NULL with n_thresholds > 0, a threshold < 1, both outputs NULL, and bases_ge NULL with n_thresholds > 0 (all of
+ * them whatever probe->n is).  bases_ge[T = 1] = ivj_coverage; the sum of bases_ge[T] over T = 1 .. max depth = ivj_overlap_bases;
+ * max_depth <= ivj_count_overlaps.  Probe order is kept; no atomics, no capacity protocol: bit-identical from run to run. */
+#define IVJ_MAX_THRESHOLDS 8
+int ivj_depth_summary(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, const int32_t* thresholds,
+                      int32_t n_thresholds, int32_t* max_depth, int64_t* bases_ge);
+/* The same on an index of ivj_index_build_dev (any form: a missing end order is completed on demand, a sweep-only index is
+ * accepted, as ivj_depth_dev); probe columns and outputs in HBM, `thresholds` on the host.  An empty index, or one whose blocks
+ * come out empty, zero-fills the outputs.  Every call derives the depth blocks, their index, a 64-bit threshold prefix table and a
+ * tree of depth maxima, and releases them before it returns (it waits for the stream): nothing is cached on the index.
+ * partition_mode 0, 1 and 2 all run in probe order and return identical arrays.  The blocks (at most 2 n) must fit the index
+ * limit of ivj_index_build_dev. */
+int ivj_depth_summary_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, const ivj_opts* opts, const int32_t* thresholds,
+                          int32_t n_thresholds, int32_t* max_depth_dev, int64_t* bases_ge_dev);
+
 /* ---- set operations on two frames, and their stats (pb.set_intersect / set_union / set_difference / set_symmetric_difference,
  * pb.jaccard) ------------------------------------------------------------------------------------------------------------------
  * U(F) = the (contig, position) pairs at least one row of F covers, under the conventions of ivj_depth: Strict rows cover

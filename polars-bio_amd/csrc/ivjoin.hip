@@ -31,6 +31,7 @@
 #include "group.hip.h"
 #include "depth.hip.h"
 #include "depth_sum.hip.h"
+#include "depth_query.hip.h"
 #include "setop.hip.h"
 
 using namespace ivj;
@@ -44,6 +45,7 @@ using namespace ivj;
 #include "host_sortscan.hip.h"
 #include "host_depth.hip.h"
 #include "host_depth_sum.hip.h"
+#include "host_depth_query.hip.h"
 #include "host_setop.hip.h"
 #include "host_stream.hip.h"
 #include "host_comm.hip.h"
@@ -750,6 +752,46 @@ int ivj_depth(ivj_ctx* ctx, const ivj_side* frame, const ivj_opts* opts, ivj_blo
     const hipError_t e = copy.finish();
     if (e != hipSuccess) { ivj_blocks_free(out); return fail(IVJ_EHIP, std::string("D2H(blocks): ") + hipGetErrorString(e)); }
     out->n = total;
+    return IVJ_OK;
+} IVJ_ABI_CATCH
+
+// ---------------------------------------------------------------- depth summary (max depth, bases at depth thresholds)
+
+int ivj_depth_summary_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, const ivj_opts* opts, const int32_t* thresholds,
+                          int32_t n_thresholds, int32_t* max_depth_dev, int64_t* bases_ge_dev) try {
+    if (!ctx || !ix) return fail(IVJ_EINVAL, "ctx or index is NULL");
+    IVJ_TRY(check_opts(opts));
+    IVJ_TRY(check_side(probe_dev, "probe"));
+    IVJ_TRY(depth_query_check(thresholds, n_thresholds, max_depth_dev, bases_ge_dev));
+    DeviceGuard g(ctx->device);
+    return depth_query_dev(ctx, ix, probe_dev, opts, thresholds, n_thresholds, max_depth_dev, bases_ge_dev);
+} IVJ_ABI_CATCH
+
+int ivj_depth_summary(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, const int32_t* thresholds,
+                      int32_t n_thresholds, int32_t* max_depth, int64_t* bases_ge) try {
+    if (!ctx) return fail(IVJ_EINVAL, "ctx is NULL");
+    IVJ_TRY(check_opts(opts));
+    IVJ_TRY(check_side(probe, "probe"));
+    IVJ_TRY(check_side(build, "build"));
+    IVJ_TRY(depth_query_check(thresholds, n_thresholds, max_depth, bases_ge));
+    if (probe->n == 0) return IVJ_OK;
+    DeviceGuard g(ctx->device);
+    DevSide dp, db;
+    IVJ_TRY(upload_side(ctx, build, db));
+    IVJ_TRY(upload_side(ctx, probe, dp));
+    IndexHolder h;
+    IVJ_TRY(index_build(ctx, &db.s, opts, 3, &h.ix));      // sweep only (no lookup tables) + the end order: what depth_core reads
+    const size_t n = (size_t)probe->n, md_bytes = align_up(n * 4), col_bytes = n * 8;
+    DevBuf out;
+    hipError_t e = hipMalloc(&out.p, md_bytes + (size_t)n_thresholds * col_bytes + 256);
+    if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(depth summary): ") + hipGetErrorString(e));
+    int32_t* d_md = max_depth ? (int32_t*)out.p : nullptr;
+    int64_t* d_bg = n_thresholds > 0 ? (int64_t*)((char*)out.p + md_bytes) : nullptr;
+    IVJ_TRY(depth_query_dev(ctx, h.ix, &dp.s, opts, thresholds, n_thresholds, d_md, d_bg));
+    HostXfer copy(ctx->stream, &ctx->xfer);
+    if (d_md) copy.d2h(max_depth, d_md, n * 4);
+    if (d_bg) copy.d2h(bases_ge, d_bg, (size_t)n_thresholds * col_bytes);
+    HIP_TRY(copy.finish());
     return IVJ_OK;
 } IVJ_ABI_CATCH
 

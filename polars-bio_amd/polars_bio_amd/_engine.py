@@ -33,7 +33,7 @@ ABI_SYMBOLS = [
     "ivj_subtract", "ivj_complement", "ivj_pieces_free", "ivj_subtract_dev",
     "ivj_merge", "ivj_merged_free", "ivj_cluster", "ivj_coverage", "ivj_cluster_dev", "ivj_merge_dev", "ivj_coverage_dev",
     "ivj_overlap_bases", "ivj_overlap_bases_dev",
-    "ivj_depth", "ivj_blocks_free", "ivj_depth_dev",
+    "ivj_depth", "ivj_blocks_free", "ivj_depth_dev", "ivj_depth_summary", "ivj_depth_summary_dev",
     "ivj_setop", "ivj_regions_free", "ivj_set_stats", "ivj_setop_dev", "ivj_set_stats_dev",
     "ivj_stream_open", "ivj_stream_submit", "ivj_stream_flush", "ivj_stream_set_nearest_ignore", "ivj_stream_close",
     "ivj_dev_alloc", "ivj_dev_free", "ivj_memcpy_h2d", "ivj_memcpy_d2h",
@@ -223,6 +223,8 @@ def load_library() -> C.CDLL:
         L.ivj_coverage_dev.argtypes = [vp, vp, P, O, vp]
         L.ivj_overlap_bases.argtypes = [vp, P, P, O, vp]
         L.ivj_overlap_bases_dev.argtypes = [vp, vp, P, O, vp]
+        L.ivj_depth_summary.argtypes = [vp, P, P, O, vp, C.c_int32, vp, vp]
+        L.ivj_depth_summary_dev.argtypes = [vp, vp, P, O, vp, C.c_int32, vp, vp]
         L.ivj_stream_open.argtypes = [vp, P, O, C.c_int, C.c_int64, C.POINTER(vp)]
         L.ivj_stream_submit.argtypes = [vp, P, C.POINTER(_StreamResult)]
         L.ivj_stream_flush.argtypes = [vp, C.POINTER(_StreamResult)]
@@ -685,6 +687,22 @@ class Engine:
         del keep_p, keep_b
         return bases
 
+    def depth_summary(self, probe, build, strict: bool, n_contigs: int, thresholds=(1,), partition_mode: int = 0, want_max: bool = True):
+        """pb.depth_summary: -> (max_depth int32[n], bases_ge int64[K, n]): per probe row the largest number of build rows of its
+        contig that cover one of its positions, and per threshold T = thresholds[k] the number of its positions covered by at
+        least T build rows (row k of bases_ge, the caller's order).  want_max=False: thresholds only, max_depth comes back None."""
+        ps, keep_p = _host_side(*probe)
+        bs, keep_b = _host_side(*build)
+        o = make_opts(strict, n_contigs, partition_mode=partition_mode)
+        thr = np.ascontiguousarray(np.asarray(list(thresholds), dtype=np.int64).astype(np.int32))
+        k = int(thr.shape[0])
+        md = np.empty(ps.n, np.int32) if want_max else None
+        bg = np.empty((k, ps.n), np.int64)
+        _check(self.L, self.L.ivj_depth_summary(self.h, C.byref(ps), C.byref(bs), C.byref(o), thr.ctypes.data if k else None, k,
+                                                 md.ctypes.data if want_max else None, bg.ctypes.data if k else None), "ivj_depth_summary")
+        del keep_p, keep_b
+        return md, bg
+
     def _pieces(self, fn, name, a, b, strict, n_contigs, partition_mode=0):
         sa, keep_a = _host_side(*a)
         sb, keep_b = _host_side(*b)
@@ -898,6 +916,13 @@ class Engine:
     def coverage_dev(self, ix: DeviceIndex, probe: _Side, opts: _Opts, coverage_ptr: int):
         _check(self.L, self.L.ivj_coverage_dev(self.h, ix.handle, C.byref(probe), C.byref(opts), C.c_void_p(coverage_ptr)),
                "ivj_coverage_dev")
+
+    def depth_summary_dev(self, ix: DeviceIndex, probe: _Side, opts: _Opts, thresholds, max_depth_ptr: int, bases_ge_ptr: int):
+        """thresholds: host ints; max_depth_ptr / bases_ge_ptr: device addresses (0 = NULL) of int32[n] / column-major int64[K, n]."""
+        thr = np.ascontiguousarray(np.asarray(list(thresholds), dtype=np.int64).astype(np.int32))
+        k = int(thr.shape[0])
+        _check(self.L, self.L.ivj_depth_summary_dev(self.h, ix.handle, C.byref(probe), C.byref(opts), thr.ctypes.data if k else None, k,
+                                                     C.c_void_p(max_depth_ptr or None), C.c_void_p(bases_ge_ptr or None)), "ivj_depth_summary_dev")
 
     def overlap_bases_dev(self, ix: DeviceIndex, probe: _Side, opts: _Opts, bases_ptr: int):
         _check(self.L, self.L.ivj_overlap_bases_dev(self.h, ix.handle, C.byref(probe), C.byref(opts), C.c_void_p(bases_ptr)),

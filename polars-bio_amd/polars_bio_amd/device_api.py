@@ -196,6 +196,31 @@ class DeviceJoin:
                 ix.close()
         return bases
 
+    def depth_summary(self, probe: DeviceSide, build: DeviceSide, strict: bool, n_contigs: int, thresholds=(1,), index=None,
+                      out_max=None, out_bases=None, partition_mode: int = 0):
+        """Per probe row the maximum depth of the build side under it and, per threshold T, its positions covered at least T deep
+        -> (max_depth int32[n], bases_ge int64[K, n]) tensors in HBM, row k of bases_ge = thresholds[k].  ``index``: a prebuilt
+        index of the build side (any form); ``out_max`` / ``out_bases``: caller buffers of those shapes (contiguous)."""
+        torch = self.torch
+        thresholds = [int(t) for t in thresholds]
+        opts = make_opts(strict, n_contigs, partition_mode=partition_mode)
+        own = index is None
+        ix = self.engine.index_build_dev(build.as_c(), opts, True, sweep_only=True) if own else index
+        try:
+            dev = probe.start.device
+            md = out_max if out_max is not None else torch.empty(probe.n, dtype=torch.int32, device=dev)
+            bg = out_bases if out_bases is not None else torch.empty((len(thresholds), probe.n), dtype=torch.int64, device=dev)
+            if md.dtype != torch.int32 or tuple(md.shape) != (probe.n,) or not md.is_contiguous():
+                raise ValueError("out_max must be a contiguous int32 tensor of probe.n elements")
+            if bg.dtype != torch.int64 or tuple(bg.shape) != (len(thresholds), probe.n) or not bg.is_contiguous():
+                raise ValueError("out_bases must be a contiguous int64 tensor of shape (len(thresholds), probe.n)")
+            if probe.n > 0:      # a tensor without elements has no address, and the entry refuses NULL outputs whatever the row count
+                self.engine.depth_summary_dev(ix, probe.as_c(), opts, thresholds, md.data_ptr(), bg.data_ptr() if thresholds else 0)
+        finally:
+            if own:
+                ix.close()
+        return md, bg
+
     def merge(self, frame: DeviceSide, strict: bool, n_contigs: int, min_dist: int = 0, out=None):
         """Merged intervals of one frame -> (contig, start, end int32, n_intervals int64) tensors.
         ``out``: optional preallocated 4-tuple (views of the first n_merged elements are returned)."""

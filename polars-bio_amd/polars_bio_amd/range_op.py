@@ -27,7 +27,7 @@ from .constants import DEFAULT_INTERVAL_COLUMNS
 
 logger = logging.getLogger("polars_bio_amd")
 
-__all__ = ["overlap", "overlap_batches", "count_overlaps_batches", "nearest_batches", "nearest", "count_overlaps", "coverage", "mean_depth", "merge", "cluster", "complement", "subtract",
+__all__ = ["overlap", "overlap_batches", "count_overlaps_batches", "nearest_batches", "nearest", "count_overlaps", "coverage", "mean_depth", "depth_summary", "merge", "cluster", "complement", "subtract",
            "set_intersect", "set_union", "set_difference", "set_symmetric_difference", "jaccard",
            "FilterOp", "RangeOp", "OverlapOutputMode"]
 
@@ -627,6 +627,62 @@ def mean_depth(
     mean = np.divide(bases.astype(np.float64), length.astype(np.float64), out=np.zeros(len(bases), np.float64), where=has_positions)
     t = t1.append_column("bases", pa.array(bases, type=pa.int64()))
     t = t.append_column("mean_depth", pa.array(mean, type=pa.float64(), mask=~has_positions))
+    return A.from_arrow(t, output_type, zero_based)
+
+
+def _validate_thresholds(thresholds) -> list:
+    """-> the thresholds as a list of ints: an iterable of at most 8 distinct ints >= 1 (empty: max_depth only)."""
+    if isinstance(thresholds, (str, bytes)) or not hasattr(thresholds, "__iter__"):
+        raise ValueError("thresholds must be an iterable of ints >= 1")
+    out = []
+    for t in thresholds:
+        if isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, np.integer)):
+            raise ValueError(f"thresholds must be ints >= 1, got {t!r}")
+        if int(t) < 1 or int(t) > 0x7fffffff:
+            raise ValueError(f"thresholds must be ints in 1 .. 2^31 - 1, got {t!r}")
+        out.append(int(t))
+    if len(out) > 8:
+        raise ValueError(f"at most 8 thresholds per call, got {len(out)}")
+    if len(set(out)) != len(out):
+        raise ValueError(f"thresholds must be distinct, got {out}")
+    return out
+
+
+def depth_summary(
+    df1,
+    df2,
+    thresholds=(1,),
+    suffixes: tuple = ("_1", "_2"),
+    on_cols: Union[list, None] = None,
+    cols1: Union[list, None] = ["chrom", "start", "end"],
+    cols2: Union[list, None] = ["chrom", "start", "end"],
+    output_type: str = "polars.LazyFrame",
+    read_options=None,
+    projection_pushdown: bool = True,
+):
+    """How deep df2 piles up over every df1 interval: ``max_depth`` = the largest number of df2 intervals of its contig that
+    cover one position of the df1 row, and per threshold T ``bases_ge_<T>`` = the number of the row's positions that at least T
+    df2 intervals cover.  The per-target columns of ``mosdepth --thresholds`` and of ``bedtools map -o max`` on a bedGraph of
+    ``pb.depth(df2)``, for an interval frame of reads or fragments, in one call.
+
+    Identities: ``bases_ge_1`` = ``pb.coverage``'s column; the sum of ``bases_ge_<T>`` over T = 1 .. max(max_depth) =
+    ``pb.mean_depth``'s ``bases``; ``max_depth`` <= ``pb.count_overlaps``'s count; ``max_depth`` = 0 exactly where the coverage
+    is 0; ``bases_ge_<T>`` does not grow with T and is positive exactly where T <= ``max_depth``.
+
+    Output = df1 columns + ``max_depth`` (Int64) + one ``bases_ge_<T>`` (Int64) per threshold, in the given order, df1 row
+    order kept.  ``thresholds``: an iterable of at most 8 distinct ints >= 1; empty gives ``max_depth`` only.  0-based frames
+    are half-open (intervals that only touch share nothing), 1-based frames closed.  Rows of either frame that cover no
+    position, and rows with a null chrom, share nothing (such df1 rows get 0 in every column).
+    ``on_cols``: only df2 intervals of the df1 row's group of equal (chrom, on values) count; a null on-value matches nothing."""
+    on_cols = _validate_overlap_input(cols1, cols2, on_cols, suffixes, output_type)
+    thresholds = _validate_thresholds(thresholds)
+    _check_on_cols_present(on_cols, df1, df2)
+    zero_based = validate_coordinate_systems(df1, df2)
+    t1, t2, probe, build, n_contigs, _keys = _prepare(df1, df2, cols1, cols2, on_cols)
+    max_depth, bases_ge = default_engine().depth_summary(probe, build, strict=zero_based, n_contigs=n_contigs, thresholds=thresholds)
+    t = t1.append_column("max_depth", pa.array(max_depth.astype(np.int64), type=pa.int64()))
+    for k, thr in enumerate(thresholds):
+        t = t.append_column(f"bases_ge_{thr}", pa.array(bases_ge[k], type=pa.int64()))
     return A.from_arrow(t, output_type, zero_based)
 
 
