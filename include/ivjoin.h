@@ -436,6 +436,40 @@ int ivj_setop_dev(ivj_ctx* ctx, ivj_index* ix_a, ivj_index* ix_b, const ivj_opts
                   int32_t* start_dev, int32_t* end_dev, int64_t* n_regions);
 int ivj_set_stats_dev(ivj_ctx* ctx, ivj_index* ix_a, ivj_index* ix_b, const ivj_opts* opts, int64_t bases[3], int64_t* n_intersections);
 
+/* ---- N frames as position sets (pb.multi_intersect, pb.consensus) ------------------------------------------------------------
+ * F frames, 1 <= F <= IVJ_MAX_FRAMES, each read as its set U(F_f) under the conventions of the set operations above.
+ * mask(c, x) = the frames that cover position x of contig c, bit f for frame f.  With k = min_frames in 1 .. F:
+ *   IVJ_MULTI_SEGMENTS   the maximal runs of positions with ONE mask of at least k bits (bedtools multiinter): neighbouring
+ *                        segments differ in mask unless a gap, a dropped segment or a contig boundary lies between them; segments
+ *                        that pass the k filter are not merged with each other.  Where a row of frame 0 ends and a row of frame 1
+ *                        starts is a segment boundary; two touching rows of one frame are not.
+ *   IVJ_MULTI_CONSENSUS  the maximal runs of positions covered by at least k frames (runs that touch are one region): k = 1 is
+ *                        the N-way union, k = F the N-way intersection.
+ * (contig id, start) order, bounds in the mode's own convention, at most 2 x the summed union runs <= 2 x the summed rows regions;
+ * bit-identical from run to run.  IVJ_EINVAL: n_frames outside 1 .. IVJ_MAX_FRAMES, min_frames outside 1 .. n_frames, an unknown
+ * mode, an index over another dictionary than opts->n_contigs. */
+#define IVJ_MAX_FRAMES 64
+#define IVJ_MULTI_SEGMENTS 0
+#define IVJ_MULTI_CONSENSUS 1
+typedef struct {
+    int64_t n;
+    int32_t* contig;
+    int32_t* start;
+    int32_t* end;
+    uint64_t* mask;      /* NULL for IVJ_MULTI_CONSENSUS */
+} ivj_segments;
+
+/* Host path: `frames` is an array of n_frames sides (an empty side is legal); library-owned buffers, released by ivj_segments_free. */
+int ivj_multi_inter(ivj_ctx* ctx, const ivj_side* frames, int32_t n_frames, const ivj_opts* opts, int32_t min_frames, int32_t mode,
+                    ivj_segments* out);
+void ivj_segments_free(ivj_segments* s);
+/* Device path over n_frames indexes of ivj_index_build_dev (any with_end_order: a missing end order is completed on demand, sweep-only
+ * indexes are accepted; a NULL entry = an empty frame).  The capacity protocol of ivj_setop_dev: *n always receives the total;
+ * IVJ_ECAPACITY when it exceeds `capacity`, and nothing is written then.  mask_dev (capacity x uint64) is written for
+ * IVJ_MULTI_SEGMENTS only and may be NULL for IVJ_MULTI_CONSENSUS. */
+int ivj_multi_inter_dev(ivj_ctx* ctx, ivj_index* const* ix, int32_t n_frames, const ivj_opts* opts, int32_t min_frames, int32_t mode,
+                        int64_t capacity, int32_t* contig_dev, int32_t* start_dev, int32_t* end_dev, uint64_t* mask_dev, int64_t* n);
+
 /* ---- group ids: joins keyed on extra columns (on_cols) --------------------------------------------------------------------------
  * Every kernel partitions by one int32 id per row and ignores ids outside [0, n_contigs).  A dense GROUP id over (chrom, on_col
  * values...) passed as `contig`, with n_contigs = the number of groups, makes every operation of this header run within groups.

@@ -33,6 +33,7 @@
 #include "depth_sum.hip.h"
 #include "depth_query.hip.h"
 #include "setop.hip.h"
+#include "multi.hip.h"
 
 using namespace ivj;
 
@@ -47,6 +48,7 @@ using namespace ivj;
 #include "host_depth_sum.hip.h"
 #include "host_depth_query.hip.h"
 #include "host_setop.hip.h"
+#include "host_multi.hip.h"
 #include "host_stream.hip.h"
 #include "host_comm.hip.h"
 #include "host_group.hip.h"
@@ -869,6 +871,69 @@ int ivj_set_stats(ivj_ctx* ctx, const ivj_side* a, const ivj_side* b, const ivj_
     SetSides s;
     IVJ_TRY(setop_sides(ctx, a, b, opts, s));
     return set_stats_core(ctx, s.ha.ix, s.hb.ix, opts, bases, n_intersections);
+} IVJ_ABI_CATCH
+
+// ---------------------------------------------------------------- N frames as position sets (segments, consensus)
+
+int ivj_multi_inter_dev(ivj_ctx* ctx, ivj_index* const* ix, int32_t n_frames, const ivj_opts* opts, int32_t min_frames, int32_t mode,
+                        int64_t capacity, int32_t* contig_dev, int32_t* start_dev, int32_t* end_dev, uint64_t* mask_dev, int64_t* n) try {
+    if (!ctx || !n) return fail(IVJ_EINVAL, "ctx or n is NULL");
+    *n = 0;
+    IVJ_TRY(check_opts(opts));
+    if (capacity < 0) return fail(IVJ_EINVAL, "capacity < 0");
+    DeviceGuard g(ctx->device);
+    unsigned long long* mask = (unsigned long long*)mask_dev;
+    return multi_core(ctx, ix, n_frames, opts, min_frames, mode, capacity, &contig_dev, &start_dev, &end_dev, &mask, nullptr, n);
+} IVJ_ABI_CATCH
+
+void ivj_segments_free(ivj_segments* s) {
+    if (!s) return;
+    std::free(s->contig); std::free(s->start); std::free(s->end); std::free(s->mask);
+    s->contig = s->start = s->end = nullptr; s->mask = nullptr; s->n = 0;
+}
+
+int ivj_multi_inter(ivj_ctx* ctx, const ivj_side* frames, int32_t n_frames, const ivj_opts* opts, int32_t min_frames, int32_t mode,
+                    ivj_segments* out) try {
+    if (!ctx || !out) return fail(IVJ_EINVAL, "ctx or out is NULL");
+    std::memset(out, 0, sizeof(*out));
+    IVJ_TRY(check_opts(opts));
+    if (n_frames < 1 || n_frames > IVJ_MAX_FRAMES || !frames)
+        return fail(IVJ_EINVAL, "multi_inter: n_frames must be in 1 .. " + std::to_string(IVJ_MAX_FRAMES) + " and frames not NULL");
+    for (int32_t f = 0; f < n_frames; ++f) IVJ_TRY(check_side(&frames[f], "frame"));
+    std::vector<ivj_index*> ix((size_t)n_frames, nullptr);
+    // (the indexes do not exist yet: this call only refuses bad n_frames / min_frames / mode before anything is uploaded)
+    IVJ_TRY(multi_check(ix.data(), n_frames, opts, min_frames, mode));
+    DeviceGuard g(ctx->device);
+    // every frame uploaded and indexed (sweep only + the end order); an empty frame stays without an index
+    std::vector<DevSide> sides((size_t)n_frames);
+    std::vector<IndexHolder> holders((size_t)n_frames);
+    for (int32_t f = 0; f < n_frames; ++f) {
+        if (frames[f].n == 0) continue;
+        IVJ_TRY(upload_side(ctx, &frames[f], sides[f]));
+        IVJ_TRY(index_build(ctx, &sides[f].s, opts, 3, &holders[f].ix));
+        ix[f] = holders[f].ix;
+    }
+    DevBuf own;
+    int32_t *d_contig = nullptr, *d_start = nullptr, *d_end = nullptr;
+    unsigned long long* d_mask = nullptr;
+    int64_t total = 0;
+    IVJ_TRY(multi_core(ctx, ix.data(), n_frames, opts, min_frames, mode, -1, &d_contig, &d_start, &d_end, &d_mask, &own, &total));
+    if (total == 0) return IVJ_OK;
+    const bool with_mask = mode == IVJ_MULTI_SEGMENTS;
+    out->contig = (int32_t*)host_result_alloc((size_t)total * 4);
+    out->start = (int32_t*)host_result_alloc((size_t)total * 4);
+    out->end = (int32_t*)host_result_alloc((size_t)total * 4);
+    if (with_mask) out->mask = (uint64_t*)host_result_alloc((size_t)total * 8);
+    if (!out->contig || !out->start || !out->end || (with_mask && !out->mask)) { ivj_segments_free(out); return fail(IVJ_ENOMEM, "host malloc(segments)"); }
+    HostXfer copy(ctx->stream, &ctx->xfer);
+    copy.d2h(out->contig, d_contig, (size_t)total * 4);
+    copy.d2h(out->start, d_start, (size_t)total * 4);
+    copy.d2h(out->end, d_end, (size_t)total * 4);
+    if (with_mask) copy.d2h(out->mask, d_mask, (size_t)total * 8);
+    const hipError_t e = copy.finish();
+    if (e != hipSuccess) { ivj_segments_free(out); return fail(IVJ_EHIP, std::string("D2H(segments): ") + hipGetErrorString(e)); }
+    out->n = total;
+    return IVJ_OK;
 } IVJ_ABI_CATCH
 
 // ---------------------------------------------------------------- subtract / complement

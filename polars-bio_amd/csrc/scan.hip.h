@@ -36,6 +36,9 @@ struct SumOp {
 struct MaxOp {
     template <class T> __device__ __forceinline__ T operator()(T a, T b) const { return a > b ? a : b; }
 };
+struct XorOp {
+    template <class T> __device__ __forceinline__ T operator()(T a, T b) const { return a ^ b; }
+};
 
 template <class T, class Op>
 __device__ __forceinline__ T wave_inclusive_scan(T v, Op op) {

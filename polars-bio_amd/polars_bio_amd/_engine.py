@@ -35,6 +35,7 @@ ABI_SYMBOLS = [
     "ivj_overlap_bases", "ivj_overlap_bases_dev",
     "ivj_depth", "ivj_blocks_free", "ivj_depth_dev", "ivj_depth_summary", "ivj_depth_summary_dev",
     "ivj_setop", "ivj_regions_free", "ivj_set_stats", "ivj_setop_dev", "ivj_set_stats_dev",
+    "ivj_multi_inter", "ivj_segments_free", "ivj_multi_inter_dev",
     "ivj_stream_open", "ivj_stream_submit", "ivj_stream_flush", "ivj_stream_set_nearest_ignore", "ivj_stream_close",
     "ivj_dev_alloc", "ivj_dev_free", "ivj_memcpy_h2d", "ivj_memcpy_d2h",
     "ivj_comm_unique_id", "ivj_comm_create", "ivj_comm_create_local", "ivj_comm_destroy", "ivj_comm_info",
@@ -56,6 +57,10 @@ NEAREST_IGNORE_LEFT, NEAREST_IGNORE_RIGHT = 1, 2
 SETOP_INTERSECTION, SETOP_UNION, SETOP_DIFFERENCE, SETOP_SYMMETRIC_DIFFERENCE = 0, 1, 2, 3
 SETOPS = {"intersection": SETOP_INTERSECTION, "union": SETOP_UNION, "difference": SETOP_DIFFERENCE,
           "symmetric_difference": SETOP_SYMMETRIC_DIFFERENCE}
+
+# ivj_multi_inter / ivj_multi_inter_dev (include/ivjoin.h: IVJ_MAX_FRAMES, IVJ_MULTI_*)
+MAX_FRAMES = 64
+MULTI_SEGMENTS, MULTI_CONSENSUS = 0, 1
 
 ROW_COLUMNS = ("probe_idx", "build_idx", "contig", "start_1", "end_1", "start_2", "end_2")
 
@@ -116,6 +121,11 @@ class _Blocks(C.Structure):
 
 class _Regions(C.Structure):
     _fields_ = [("n", C.c_int64), ("contig", C.POINTER(C.c_int32)), ("start", C.POINTER(C.c_int32)), ("end", C.POINTER(C.c_int32))]
+
+
+class _Segments(C.Structure):
+    _fields_ = [("n", C.c_int64), ("contig", C.POINTER(C.c_int32)), ("start", C.POINTER(C.c_int32)), ("end", C.POINTER(C.c_int32)),
+                ("mask", C.POINTER(C.c_uint64))]
 
 
 class _Pieces(C.Structure):
@@ -220,6 +230,10 @@ def load_library() -> C.CDLL:
         L.ivj_set_stats.argtypes = [vp, P, P, O, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.ivj_setop_dev.argtypes = [vp, vp, vp, O, C.c_int32, C.c_int64, vp, vp, vp, C.POINTER(C.c_int64)]
         L.ivj_set_stats_dev.argtypes = [vp, vp, vp, O, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.ivj_multi_inter.argtypes = [vp, P, C.c_int32, O, C.c_int32, C.c_int32, C.POINTER(_Segments)]
+        L.ivj_segments_free.argtypes = [C.POINTER(_Segments)]
+        L.ivj_segments_free.restype = None
+        L.ivj_multi_inter_dev.argtypes = [vp, C.POINTER(vp), C.c_int32, O, C.c_int32, C.c_int32, C.c_int64, vp, vp, vp, vp, C.POINTER(C.c_int64)]
         L.ivj_coverage_dev.argtypes = [vp, vp, P, O, vp]
         L.ivj_overlap_bases.argtypes = [vp, P, P, O, vp]
         L.ivj_overlap_bases_dev.argtypes = [vp, vp, P, O, vp]
@@ -329,6 +343,19 @@ def _setop_code(op) -> int:
     if int(op) not in SETOPS.values():
         raise ValueError(f"unknown set operation {op}")
     return int(op)
+
+
+def check_multi(n_frames: int, min_frames, mode=MULTI_SEGMENTS) -> int:
+    """The argument rules of ivj_multi_inter, checked before the library is touched -> min_frames as an int."""
+    if n_frames < 1 or n_frames > MAX_FRAMES:
+        raise ValueError(f"between 1 and {MAX_FRAMES} frames are expected, got {n_frames}")
+    if isinstance(min_frames, (bool, np.bool_)) or not isinstance(min_frames, (int, np.integer)):
+        raise ValueError(f"min_frames must be an int, got {min_frames!r}")
+    if min_frames < 1 or min_frames > n_frames:
+        raise ValueError(f"min_frames must be in 1 .. {n_frames} (the number of frames), got {min_frames}")
+    if mode not in (MULTI_SEGMENTS, MULTI_CONSENSUS):
+        raise ValueError(f"mode must be MULTI_SEGMENTS (0) or MULTI_CONSENSUS (1), got {mode!r}")
+    return int(min_frames)
 
 
 def make_opts(strict: bool, n_contigs: int, k: int = 1, include_overlaps: bool = True, partition_mode: int = 0,
@@ -654,6 +681,32 @@ class Engine:
         del keep_a, keep_b
         return int(bases[0]), int(bases[1]), int(bases[2]), int(ni.value)
 
+    def multi_inter(self, frames, min_frames: int, mode: int, strict: bool, n_contigs: int):
+        """pb.multi_intersect (mode MULTI_SEGMENTS) / pb.consensus (MULTI_CONSENSUS) over a list of (contig, start, end) frames:
+        -> (contig id, start, end) int32 arrays and the uint64 membership mask per segment (bit f = frame f; None for
+        consensus), (contig id, start) order, bounds in the mode's own convention."""
+        frames = list(frames)
+        min_frames = check_multi(len(frames), min_frames, mode)
+        sides = (_Side * len(frames))()
+        keep = []
+        for f, frame in enumerate(frames):
+            side, arrays = _host_side(*frame)
+            sides[f] = side
+            keep.append(arrays)
+        o = make_opts(strict, n_contigs)
+        out = _Segments()
+        _check(self.L, self.L.ivj_multi_inter(self.h, sides, len(frames), C.byref(o), min_frames, int(mode), C.byref(out)), "ivj_multi_inter")
+        del keep
+        try:
+            n = out.n
+            with_mask = mode == MULTI_SEGMENTS
+            if n == 0:
+                return (*(np.empty(0, np.int32) for _ in range(3)), np.empty(0, np.uint64) if with_mask else None)
+            cols = tuple(np.ctypeslib.as_array(getattr(out, name), shape=(n,)).copy() for name in ("contig", "start", "end"))
+            return (*cols, np.ctypeslib.as_array(out.mask, shape=(n,)).copy() if with_mask else None)
+        finally:
+            self.L.ivj_segments_free(C.byref(out))
+
     def cluster(self, frame, strict: bool, n_contigs: int, min_dist: int = 0):
         """pb.cluster: -> (cluster id int64, cluster_start, cluster_end) per input row + number of clusters."""
         fs, keep = _host_side(*frame)
@@ -894,6 +947,22 @@ class Engine:
         if rc == -4:
             return n.value, False
         _check(self.L, rc, "ivj_setop_dev")
+        return n.value, True
+
+    def multi_inter_dev(self, indexes, opts: _Opts, min_frames: int, mode: int, capacity: int, contig_ptr: int, start_ptr: int, end_ptr: int,
+                        mask_ptr: int):
+        """-> (n, fits).  fits=False: nothing was written, grow the buffers to n.  ``indexes``: one DeviceIndex (or None = an empty
+        frame) per frame; ``mask_ptr`` may be 0 for MULTI_CONSENSUS."""
+        indexes = list(indexes)
+        min_frames = check_multi(len(indexes), min_frames, mode)
+        handles = (C.c_void_p * len(indexes))(*(None if ix is None else getattr(ix.handle, "value", ix.handle) for ix in indexes))
+        n = C.c_int64(0)
+        rc = self.L.ivj_multi_inter_dev(self.h, handles, len(indexes), C.byref(opts), min_frames, int(mode), int(capacity),
+                                        C.c_void_p(contig_ptr or None), C.c_void_p(start_ptr or None), C.c_void_p(end_ptr or None),
+                                        C.c_void_p(mask_ptr or None), C.byref(n))
+        if rc == -4:
+            return n.value, False
+        _check(self.L, rc, "ivj_multi_inter_dev")
         return n.value, True
 
     def set_stats_dev(self, ix_a: DeviceIndex, ix_b: DeviceIndex, opts: _Opts):

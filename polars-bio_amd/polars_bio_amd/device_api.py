@@ -15,7 +15,7 @@ import torch  # noqa: F401  (must precede the dlopen of libivjoin_hip.so in this
 
 from typing import Optional, Tuple
 
-from ._engine import DeviceIndex, Engine, make_opts
+from ._engine import MULTI_CONSENSUS, MULTI_SEGMENTS, DeviceIndex, Engine, check_multi, make_opts
 
 
 class DeviceSide:
@@ -297,6 +297,44 @@ class DeviceJoin:
                 ix_b.close()
         finally:
             ix_a.close()
+
+    def multi_inter(self, frames, min_frames: int, strict: bool, n_contigs: int, consensus: bool = False, indexes=None, out=None):
+        """N frames (a list of DeviceSide) as position sets.  ``consensus=False``: the maximal runs of positions covered by one set
+        of at least ``min_frames`` frames -> (contig, start, end int32, mask int64) tensors, bit f of mask = frame f (the 64 bits
+        of the engine's uint64 word: frame 63 is the sign bit; ``mask.cpu().numpy().view(numpy.uint64)`` reads them unsigned).
+        ``consensus=True``: the maximal runs covered by at least ``min_frames`` frames -> (contig, start, end).  (contig, start)
+        order.  ``indexes``: prebuilt indexes of the frames (None entries = empty frames); ``out``: optional preallocated tuple of
+        those tensors (views of the first n elements are returned); at most twice the summed rows come back."""
+        torch = self.torch
+        frames = list(frames)
+        mode = MULTI_CONSENSUS if consensus else MULTI_SEGMENTS
+        min_frames = check_multi(len(frames), min_frames, mode)
+        opts = make_opts(strict, n_contigs)
+        own = indexes is None
+        ixs = []
+        try:
+            if own:
+                for side in frames:
+                    ixs.append(self._set_index(side, opts) if side.n else None)
+            else:
+                ixs = list(indexes)
+            if out is None:
+                dev, cap = frames[0].start.device, 2 * sum(side.n for side in frames)
+                out = tuple(torch.empty(cap, dtype=torch.int32, device=dev) for _ in range(3))
+                if not consensus:
+                    out += (torch.empty(cap, dtype=torch.int64, device=dev),)
+            if len(out) != (3 if consensus else 4):
+                raise ValueError("out must hold (contig, start, end) tensors, and the 8-byte mask tensor unless consensus")
+            ptrs = [t.data_ptr() for t in out[:3]] + [out[3].data_ptr() if not consensus else 0]
+            n, fits = self.engine.multi_inter_dev(ixs, opts, min_frames, mode, min(int(t.numel()) for t in out), *ptrs)
+            if not fits:
+                raise ValueError(f"multi_inter output buffers hold fewer than {n} regions")
+        finally:
+            if own:
+                for ix in ixs:
+                    if ix is not None:
+                        ix.close()
+        return tuple(t[:n] for t in out)
 
     def subtract(self, left: DeviceSide, right: DeviceSide, strict: bool, n_contigs: int, index=None, out=None):
         """left minus the union of right -> (left row, start, end) int32 tensors of the remaining pieces."""

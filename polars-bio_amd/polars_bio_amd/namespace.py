@@ -9,7 +9,7 @@ from __future__ import annotations
 
 from . import range_op
 
-# method -> (function, takes a second frame)
+# method -> (function, takes a second frame); "frames": takes a list of further frames, the call is made on [this frame, *others]
 _ALIASES = {
     "overlap": (range_op.overlap, True), "nearest": (range_op.nearest, True), "count_overlaps": (range_op.count_overlaps, True),
     "coverage": (range_op.coverage, True), "mean_depth": (range_op.mean_depth, True), "depth_summary": (range_op.depth_summary, True),
@@ -17,6 +17,7 @@ _ALIASES = {
     "merge": (range_op.merge, False), "depth": (range_op.depth, False), "cluster": (range_op.cluster, False), "complement": (range_op.complement, False),
     "set_intersect": (range_op.set_intersect, True), "set_union": (range_op.set_union, True), "set_difference": (range_op.set_difference, True),
     "set_symmetric_difference": (range_op.set_symmetric_difference, True), "jaccard": (range_op.jaccard, True),
+    "multi_intersect": (range_op.multi_intersect, "frames"), "consensus": (range_op.consensus, "frames"),
 }
 
 
@@ -28,7 +29,13 @@ def _make_accessor(default_output: str):
             self._frame = frame
 
     def bind(name, fn, binary):
-        if binary:
+        if binary == "frames":
+            def method(self, other_dfs, *args, **kwargs):
+                kwargs.setdefault("output_type", default_output)
+                if isinstance(other_dfs, (str, bytes)) or not isinstance(other_dfs, (list, tuple)):
+                    raise ValueError("the other frames must be given as a list")
+                return fn([self._frame, *other_dfs], *args, **kwargs)
+        elif binary:
             def method(self, other_df, **kwargs):
                 kwargs.setdefault("output_type", default_output)
                 return fn(self._frame, other_df, **kwargs)
@@ -37,7 +44,8 @@ def _make_accessor(default_output: str):
                 kwargs.setdefault("output_type", default_output)
                 return fn(self._frame, **kwargs)
         method.__name__ = name
-        method.__doc__ = f"Alias of pb.{name} with this frame as the first argument.\n\n{fn.__doc__ or ''}"
+        what = "as frame 0 of [this frame, *other_dfs]" if binary == "frames" else "as the first argument"
+        method.__doc__ = f"Alias of pb.{name} with this frame {what}.\n\n{fn.__doc__ or ''}"
         return method
 
     for name, (fn, binary) in _ALIASES.items():

@@ -28,7 +28,7 @@ from .constants import DEFAULT_INTERVAL_COLUMNS
 logger = logging.getLogger("polars_bio_amd")
 
 __all__ = ["overlap", "overlap_batches", "count_overlaps_batches", "nearest_batches", "nearest", "count_overlaps", "coverage", "mean_depth", "depth_summary", "merge", "cluster", "complement", "subtract",
-           "set_intersect", "set_union", "set_difference", "set_symmetric_difference", "jaccard",
+           "set_intersect", "set_union", "set_difference", "set_symmetric_difference", "jaccard", "multi_intersect", "consensus",
            "FilterOp", "RangeOp", "OverlapOutputMode"]
 
 
@@ -781,39 +781,66 @@ def depth(
 
 # ---- set operations on two frames (setop.hip.h) -------------------------------------------------------
 
-def _set_sides(df1, df2, cols1, cols2, on_cols):
-    """Both frames as sides of a set operation -> (t1, a, b, n_contigs, dictionary, group table, on_col dictionaries).
-    _prepare gives the shared chrom dictionary.  Its on_cols groups are ranks among the keys of df2 alone (a df1 row whose
-    key df2 lacks gets -1, which is right for a join and wrong for a union), so the groups are numbered here over the rows of
-    BOTH frames, the way merge / depth number the groups of their one frame."""
-    t1, t2, a, b, n_contigs, keys = _prepare(df1, df2, cols1, cols2)
-    # the shared dictionary is in first-occurrence order; the result is in (chrom, start) order, so the ids are renumbered
-    # in sorted-name order, as encode_frame numbers the one frame of merge / depth
-    dictionary = keys[4]
-    order = pc.sort_indices(dictionary).to_numpy(zero_copy_only=False).astype(np.int64)
-    if (order != np.arange(len(order))).any():
-        rank = np.empty(len(order), np.int32)
-        rank[order] = np.arange(len(order), dtype=np.int32)
-        dictionary = pc.take(dictionary, pa.array(order))
-        a, b = ((np.where(x[0] >= 0, rank[np.maximum(x[0], 0)], -1).astype(np.int32), x[1], x[2]) for x in (a, b))
+def _set_frames(dfs, cols_list, on_cols):
+    """Frames as position sets -> (tables, sides, n_contigs, dictionary, group table, on_col dictionaries); sides[f] =
+    (contig, start, end) int32 of frame f without its rows of a null chrom (or on-value).
+    One chrom dictionary over all frames, numbered in sorted-name order: the result is in (chrom, start) order, as
+    encode_frame numbers the one frame of merge / depth.  _prepare's on_cols groups are ranks among the keys of df2 alone (a
+    df1 row whose key df2 lacks gets -1, which is right for a join and wrong for a union), so the groups are numbered here
+    over the rows of ALL frames, the way merge / depth number the groups of their one frame."""
+    tables = [A.to_arrow(df) for df in dfs]
+    cols_list = [list(DEFAULT_INTERVAL_COLUMNS if cols is None else cols) for cols in cols_list]
+    for t, cols in zip(tables, cols_list):
+        for c in cols:
+            if c not in t.column_names:
+                raise ValueError(f"column '{c}' not found in {t.column_names}")
+    encoded = [A._encode_chrom(t.column(cols[0])) for t, cols in zip(tables, cols_list)]
+    dictionary = pc.unique(pa.concat_arrays([d for d, _ in encoded]))
+    dictionary = dictionary.combine_chunks() if isinstance(dictionary, pa.ChunkedArray) else dictionary
+    dictionary = pc.take(dictionary, pc.sort_indices(dictionary))
+    n_contigs = len(dictionary)
+    sides = []
+    for (d, ids), t, cols in zip(encoded, tables, cols_list):
+        if len(ids):
+            remap = pc.index_in(d, value_set=dictionary).to_numpy(zero_copy_only=False).astype(np.int32)
+            ids = np.where(ids >= 0, remap[np.maximum(ids, 0)], -1).astype(np.int32)
+        sides.append((ids, A._coord_to_i32(t.column(cols[1]), cols[1]), A._coord_to_i32(t.column(cols[2]), cols[2])))
     gchrom = dicts = None
     if on_cols:
-        for t in (t1, t2):
+        for t in tables:
             missing = [c for c in on_cols if c not in t.column_names]
             assert not missing, f"on_cols {missing} not found in {t.column_names}"
-        (codes1, codes2), cards, dicts, _ = A.encode_on_cols([t1, t2], on_cols)
-        n1 = len(a[0])
-        both = tuple(np.concatenate([x, y]) for x, y in zip(a, b))
-        codes = [np.concatenate([c1, c2]) for c1, c2 in zip(codes1, codes2)]
+        codes_by_frame, cards, dicts, _ = A.encode_on_cols(tables, on_cols)
+        bounds = np.concatenate([[0], np.cumsum([len(x[0]) for x in sides])])
+        every = tuple(np.concatenate([x[k] for x in sides]) for k in range(3))
+        codes = [np.concatenate([cf[j] for cf in codes_by_frame]) for j in range(len(on_cols))]
         empty = (np.empty(0, np.int32),) * 3
-        _, both, groups, table = A.group_sides(empty, both, n_contigs, [np.empty(0, np.int32)] * len(on_cols), codes, cards, on_cols)
-        a, b = (both[0][:n1], a[1], a[2]), (both[0][n1:], b[1], b[2])
+        _, every, groups, table = A.group_sides(empty, every, n_contigs, [np.empty(0, np.int32)] * len(on_cols), codes, cards, on_cols)
+        sides = [(every[0][bounds[f]:bounds[f + 1]], x[1], x[2]) for f, x in enumerate(sides)]
         n_contigs, gchrom = max(groups, 1), table
 
     def known(side):                                      # rows with a null chrom (or on-value) belong to no contig
         keep = side[0] >= 0
         return side if keep.all() else tuple(np.ascontiguousarray(x[keep]) for x in side)
-    return t1, known(a), known(b), n_contigs, dictionary, gchrom, dicts
+    return tables, [known(x) for x in sides], n_contigs, dictionary, gchrom, dicts
+
+
+def _set_sides(df1, df2, cols1, cols2, on_cols):
+    """Both frames as sides of a set operation -> (t1, a, b, n_contigs, dictionary, group table, on_col dictionaries)."""
+    tables, (a, b), n_contigs, dictionary, gchrom, dicts = _set_frames([df1, df2], [cols1, cols2], on_cols)
+    return tables[0], a, b, n_contigs, dictionary, gchrom, dicts
+
+
+def _regions_table(t1, cols, c, s, e, dictionary, gchrom, dicts, on_cols):
+    """(contig id, start, end) of a position-set result -> the columns (chrom, start, end, <on_cols...>) named from ``cols``"""
+    c = np.ascontiguousarray(c, np.int32)
+    chrom_ids = c if gchrom is None else A.H.take(np.ascontiguousarray(gchrom[:, 0]), c)
+    data = {cols[0]: pc.cast(pc.take(dictionary, pa.array(chrom_ids, type=pa.int32())), pa.string()),
+            cols[1]: pa.array(s.astype(np.int64)), cols[2]: pa.array(e.astype(np.int64))}
+    for j, name in enumerate(on_cols or ()):
+        values = pc.take(dicts[j], pa.array(A.H.take(np.ascontiguousarray(gchrom[:, 1 + j]), c), type=pa.int32()))
+        data[name] = A.cast_on_values(values, t1.schema.field(name).type)
+    return data
 
 
 def _set_operation(op, df1, df2, on_cols, cols1, cols2, output_type):
@@ -823,14 +850,7 @@ def _set_operation(op, df1, df2, on_cols, cols1, cols2, output_type):
     t1, a, b, n_contigs, dictionary, gchrom, dicts = _set_sides(df1, df2, cols1, cols2, on_cols)
     cols = list(DEFAULT_INTERVAL_COLUMNS if cols1 is None else cols1)
     c, s, e = default_engine().setop(a, b, op, strict=zero_based, n_contigs=n_contigs)
-    c = np.ascontiguousarray(c, np.int32)
-    chrom_ids = c if gchrom is None else A.H.take(np.ascontiguousarray(gchrom[:, 0]), c)
-    data = {cols[0]: pc.cast(pc.take(dictionary, pa.array(chrom_ids, type=pa.int32())), pa.string()),
-            cols[1]: pa.array(s.astype(np.int64)), cols[2]: pa.array(e.astype(np.int64))}
-    for j, name in enumerate(on_cols or ()):
-        values = pc.take(dicts[j], pa.array(A.H.take(np.ascontiguousarray(gchrom[:, 1 + j]), c), type=pa.int32()))
-        data[name] = A.cast_on_values(values, t1.schema.field(name).type)
-    return A.from_arrow(pa.table(data), output_type, zero_based)
+    return A.from_arrow(pa.table(_regions_table(t1, cols, c, s, e, dictionary, gchrom, dicts, on_cols)), output_type, zero_based)
 
 
 _SET_DOC = """{what}
@@ -892,6 +912,95 @@ def jaccard(df1, df2, on_cols: Union[list, None] = None, cols1: Union[list, None
                     "jaccard": pa.array([both / union if union else None], type=pa.float64()),
                     "n_intersections": pa.array([n_int], type=pa.int64())})
     return A.from_arrow(res, output_type, zero_based)
+
+
+# ---- N frames as position sets (multi.hip.h) ------------------------------------------------------------
+
+_MULTI_DOC = """
+
+    Every frame is read as the set operations read it: the SET of (chrom, position) its rows cover, 0-based frames half-open,
+    1-based frames closed; rows that cover no position and rows with a null chrom (or a null on-value) contribute nothing.  All
+    frames must share one coordinate system, which is set on the result.  ``frames``: a list of 1 .. 64 frames; ``cols`` names
+    the interval columns of every frame; ``on_cols``: positions match within groups of equal (chrom, on values) only."""
+
+
+def _multi_frames(frames, min_frames, on_cols, cols, output_type):
+    """the shared front of multi_intersect / consensus: every argument check (ValueError, before the engine is touched), then
+    the frames as sides -> (min_frames, on_cols, cols, zero_based, t1, sides, n_contigs, dictionary, group table, dictionaries)"""
+    from ._engine import check_multi
+    if isinstance(frames, (str, bytes)) or not isinstance(frames, (list, tuple)):
+        raise ValueError("frames must be a list of interval frames")
+    frames = list(frames)
+    min_frames = check_multi(len(frames), min_frames)
+    on_cols = _validate_overlap_input(cols, cols, on_cols, ("_1", "_2"), output_type)
+    _check_on_cols_present(on_cols, *frames)
+    zero_based = validate_coordinate_system_single(frames[0]) if len(frames) == 1 else None
+    for other in frames[1:]:
+        zero_based = validate_coordinate_systems(frames[0], other)
+    cols = list(DEFAULT_INTERVAL_COLUMNS if cols is None else cols)
+    tables, sides, n_contigs, dictionary, gchrom, dicts = _set_frames(frames, [cols] * len(frames), on_cols)
+    return min_frames, on_cols, cols, zero_based, tables[0], sides, n_contigs, dictionary, gchrom, dicts
+
+
+def multi_intersect(frames, min_frames: int = 1, names: Union[list, None] = None, on_cols: Union[list, None] = None,
+                    cols: Union[list, None] = ["chrom", "start", "end"], output_type: str = "polars.LazyFrame"):
+    if names is not None:
+        names = _check_names(names, frames, on_cols, cols)
+    min_frames, on_cols, cols, zero_based, t1, sides, n_contigs, dictionary, gchrom, dicts = _multi_frames(frames, min_frames, on_cols, cols, output_type)
+    from ._engine import MULTI_SEGMENTS
+    c, s, e, mask = default_engine().multi_inter(sides, min_frames, MULTI_SEGMENTS, strict=zero_based, n_contigs=n_contigs)
+    data = _regions_table(t1, cols, c, s, e, dictionary, gchrom, dicts, on_cols)
+    mask = np.ascontiguousarray(mask, np.uint64)
+    bits = np.unpackbits(mask.view(np.uint8).reshape(-1, 8), axis=1, bitorder="little") if mask.size else np.zeros((0, 64), np.uint8)
+    data["n_frames"] = pa.array(bits.sum(axis=1, dtype=np.int64), type=pa.int64())
+    data["mask"] = pa.array(mask, type=pa.uint64())
+    for f, name in enumerate(names or ()):
+        data[name] = pa.array(bits[:, f].astype(bool), type=pa.bool_())
+    return A.from_arrow(pa.table(data), output_type, zero_based)
+
+
+def _check_names(names, frames, on_cols, cols) -> list:
+    """names: one distinct string per frame, none colliding with the other output columns (ValueError) -> names as a list"""
+    if isinstance(names, (str, bytes)) or not isinstance(names, (list, tuple)) or not all(isinstance(x, str) for x in names):
+        raise ValueError("names must be a list of strings, one per frame")
+    names = list(names)
+    if isinstance(frames, (list, tuple)) and len(names) != len(frames):
+        raise ValueError(f"names must hold one string per frame: {len(frames)} frames, {len(names)} names")
+    if len(set(names)) != len(names):
+        raise ValueError("names holds a name twice")
+    on = [on_cols] if isinstance(on_cols, str) else list(on_cols or ())
+    taken = set(DEFAULT_INTERVAL_COLUMNS if cols is None else cols) | set(on) | {"n_frames", "mask"}
+    bad = [x for x in names if x in taken]
+    if bad:
+        raise ValueError(f"names collide with other output columns: {bad}")
+    return names
+
+
+multi_intersect.__doc__ = """For each stretch of the genome, which of the N frames cover it (``bedtools multiinter``): the maximal
+    runs of positions covered by the same non-empty set of frames, in (chrom, on values, start) order.
+
+    Output: (chrom, start: Int64, end: Int64, <on_cols...>, n_frames: Int64, mask: UInt64), named from ``cols``; bit f of
+    ``mask`` is set where ``frames[f]`` covers the segment and ``n_frames`` is its popcount.  With ``names`` (one distinct string
+    per frame, none of them another output column) one Boolean column per frame follows.  Two adjacent segments always differ in
+    ``mask``: where a row of frame 0 ends and a row of frame 1 starts is a segment boundary, two touching rows of the same frame
+    are not.  Segments covered by fewer than ``min_frames`` frames are dropped; the remaining ones are not merged
+    (``consensus`` merges them).""" + _MULTI_DOC
+
+
+def consensus(frames, min_frames: int, on_cols: Union[list, None] = None, cols: Union[list, None] = ["chrom", "start", "end"],
+              output_type: str = "polars.LazyFrame"):
+    min_frames, on_cols, cols, zero_based, t1, sides, n_contigs, dictionary, gchrom, dicts = _multi_frames(frames, min_frames, on_cols, cols, output_type)
+    from ._engine import MULTI_CONSENSUS
+    c, s, e, _ = default_engine().multi_inter(sides, min_frames, MULTI_CONSENSUS, strict=zero_based, n_contigs=n_contigs)
+    return A.from_arrow(pa.table(_regions_table(t1, cols, c, s, e, dictionary, gchrom, dicts, on_cols)), output_type, zero_based)
+
+
+consensus.__doc__ = """Consensus regions of N frames (DiffBind / GenomicRanges "consensus peaks"): the maximal runs of positions
+    covered by at least ``min_frames`` of the frames; runs that touch are one region.  ``min_frames=1`` is the N-way union,
+    ``min_frames=len(frames)`` the N-way intersection.
+
+    Output: (chrom, start: Int64, end: Int64, <on_cols...>), named from ``cols``, in (chrom, on values, start) order -- the
+    columns and order of the set operations.""" + _MULTI_DOC
 
 
 def cluster(
