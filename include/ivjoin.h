@@ -228,6 +228,55 @@ int ivj_count_overlaps_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_de
 int ivj_nearest_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev,
                     const ivj_opts* opts, int32_t* idx_dev, int64_t* dist_dev, int32_t* n_found_dev);
 
+/* ---- overlap thresholds: pb.overlap / pb.count_overlaps with min_overlap, min_frac1, min_frac2 -------------------------------------
+ * (bedtools intersect -f / -F / -r and a minimum base count).  For a probe (df1) row a and a build (df2) row b of one contig (one
+ * group, when the contig column carries group ids):
+ *   ov(a, b) = min(a.end, b.end) - max(a.start, b.start)      IVJ_FILTER_STRICT, 0-based half-open;  + 1 for IVJ_FILTER_WEAK, 1-based closed
+ *   len(r)   = r.end - r.start                                                                      + 1 for IVJ_FILTER_WEAK
+ * The front door offers three optional thresholds, all of which must hold (logical AND):
+ *   min_overlap  int >= 1           the pair is kept iff ov >= min_overlap
+ *   min_frac1    float in (0, 1]    ... iff ov >= 1 and ov / len(a) >= min_frac1, the division evaluated in IEEE float64 (bedtools -f)
+ *   min_frac2    float in (0, 1]    the same test against len(b) (bedtools -F); both = -f X -F Y, both equal = -r
+ * Any set threshold implies ov >= 1: rows that cover no position (zero-length rows, start > end) never match on either side,
+ * intervals that only touch never match, rows outside the dictionary (a null chrom or on-value) never match.  An "either fraction
+ * suffices" mode (bedtools -e) does not exist; the streaming entries (ivj_stream_*, the Arrow-stream entries) and the multi-rank
+ * entries take no thresholds.
+ * The library sees integers only.  The caller turns each fraction f into a per-row minimum base count m(r) = the smallest integer
+ * m >= 1 with m / len(r) >= f in float64 -- ceil(f * len), corrected by one in either direction with the literal division test (IEEE
+ * division is monotone in m, so one step each way suffices) -- and "never" for rows with len <= 0.  Minima are uint32: 0 = no
+ * requirement, 0xffffffff = never (a closed row can have len = 2^31: ov and the comparison are evaluated in 64 bits).  The test the
+ * kernels apply to a pair is the single comparison
+ *   ov >= max(1, min_overlap, probe_min[a], build_min[b])           and no match at all where that maximum is 0xffffffff.
+ * probe_min: probe->n values, indexed by the row's position in the probe columns (not by row_id).  build_min: one value per build
+ * row, indexed by the row the index reports for it (its position in the build columns; for an index built from a side with row_id,
+ * ids outside [0, build rows) never match).  The pointers live in the same memory space as the sides.  A struct with nothing set
+ * (min_overlap 0, both pointers NULL) is IVJ_EINVAL: the plain entries exist for that.  (New entries and a new struct change no
+ * existing struct or signature: IVJ_ABI_VERSION stays.) */
+typedef struct {
+    uint32_t min_overlap;
+    const uint32_t* probe_min;   /* NULL = none */
+    const uint32_t* build_min;   /* NULL = none */
+} ivj_thresholds;
+
+/* Host path: the pairs as ivj_overlap returns them (library-owned, ivj_pairs_free); count, scan, then emit into an exactly sized
+ * buffer.  The pairs of one probe row are contiguous and ordered by (build.start, build row); probe rows appear in input order, or
+ * bucket by bucket where the probe side was partitioned (ivj_opts.partition_mode 0 on large inputs, 1, 5, 6; 2 never partitions).
+ * The output is identical from run to run. */
+int ivj_overlap_thresh(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, const ivj_thresholds* thr,
+                       ivj_pairs* out);
+/* counts[i] = the kept pairs of probe row i, probe order kept; caller buffer of probe->n. */
+int ivj_count_overlaps_thresh(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, const ivj_thresholds* thr,
+                              int64_t* counts);
+/* Device path on an index of ivj_index_build_dev (any with_end_order but the sweep-only form).  The capacity contract of
+ * ivj_overlap_fused_dev: *n_pairs always receives the total; IVJ_ECAPACITY when it exceeds `capacity`, and nothing is written then.
+ * NULL buffers with capacity 0 = count only (IVJ_OK).  Candidate ranges of any length are handled here: there is no hand-over to
+ * another kernel.  Blocks until the total is known. */
+int ivj_overlap_thresh_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, const ivj_opts* opts, const ivj_thresholds* thr_dev,
+                           int32_t* probe_idx_dev, int32_t* build_idx_dev, int64_t capacity, int64_t* n_pairs);
+/* Per-probe counts only (no pair is enumerated to HBM); enqueued on the context's stream. */
+int ivj_count_overlaps_thresh_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, const ivj_opts* opts, const ivj_thresholds* thr_dev,
+                                  int64_t* counts_dev);
+
 /* ---- row materialisation -------------------- *
  * The step right after the join: gather the columns of both sides for every emitted pair     *
  * (reference: the renaming SELECT of src/operation.rs:272-301 over the joined batches).      *

@@ -34,6 +34,7 @@
 #include "depth_query.hip.h"
 #include "setop.hip.h"
 #include "multi.hip.h"
+#include "thresh.hip.h"
 
 using namespace ivj;
 
@@ -49,6 +50,7 @@ using namespace ivj;
 #include "host_depth_query.hip.h"
 #include "host_setop.hip.h"
 #include "host_multi.hip.h"
+#include "host_thresh.hip.h"
 #include "host_stream.hip.h"
 #include "host_comm.hip.h"
 #include "host_group.hip.h"
@@ -1143,6 +1145,88 @@ int ivj_count_overlaps(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* buil
     hipError_t e = hipMalloc(&dc.p, (size_t)probe->n * 8);
     if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(counts): ") + hipGetErrorString(e));
     IVJ_TRY(count_overlaps_dev(ctx, h.ix, &dp.s, opts, (int64_t*)dc.p));
+    HostXfer copy(ctx->stream, &ctx->xfer);
+    copy.d2h(counts, dc.p, (size_t)probe->n * 8);
+    HIP_TRY(copy.finish());
+    return IVJ_OK;
+} IVJ_ABI_CATCH
+
+// ---------------------------------------------------------------- overlap thresholds (thresh.hip.h, host_thresh.hip.h)
+
+int ivj_overlap_thresh_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, const ivj_opts* opts, const ivj_thresholds* thr_dev,
+                           int32_t* probe_idx_dev, int32_t* build_idx_dev, int64_t capacity, int64_t* n_pairs) try {
+    if (!ctx || !ix || !n_pairs) return fail(IVJ_EINVAL, "ctx, index or n_pairs is NULL");
+    IVJ_TRY(check_opts(opts));
+    IVJ_TRY(check_side(probe_dev, "probe"));
+    IVJ_TRY(check_thresholds(thr_dev));
+    if (capacity < 0 || (capacity > 0 && (!probe_idx_dev || !build_idx_dev))) return fail(IVJ_EINVAL, "bad output buffers");
+    DeviceGuard g(ctx->device);
+    return overlap_thresh_dev(ctx, ix, probe_dev, opts, thr_dev, probe_idx_dev, build_idx_dev, capacity, n_pairs);
+} IVJ_ABI_CATCH
+
+int ivj_count_overlaps_thresh_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, const ivj_opts* opts, const ivj_thresholds* thr_dev,
+                                  int64_t* counts_dev) try {
+    if (!ctx || !ix) return fail(IVJ_EINVAL, "ctx or index is NULL");
+    IVJ_TRY(check_opts(opts));
+    IVJ_TRY(check_side(probe_dev, "probe"));
+    IVJ_TRY(check_thresholds(thr_dev));
+    if (probe_dev->n > 0 && !counts_dev) return fail(IVJ_EINVAL, "counts is NULL");
+    DeviceGuard g(ctx->device);
+    ThreshPlan plan;
+    return thresh_count(ctx, ix, probe_dev, opts, thr_dev, counts_dev, false, plan, nullptr);
+} IVJ_ABI_CATCH
+
+int ivj_overlap_thresh(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, const ivj_thresholds* thr,
+                       ivj_pairs* out) try {
+    if (!ctx || !out) return fail(IVJ_EINVAL, "ctx or out is NULL");
+    out->n_pairs = 0; out->probe_idx = nullptr; out->build_idx = nullptr;
+    IVJ_TRY(check_opts(opts));
+    IVJ_TRY(check_side(probe, "probe"));
+    IVJ_TRY(check_side(build, "build"));
+    IVJ_TRY(check_thresholds(thr));
+    DeviceGuard g(ctx->device);
+    ThreshHost H;
+    IVJ_TRY(thresh_upload(ctx, probe, build, opts, thr, H));
+    ThreshPlan plan;
+    int64_t total = 0;
+    IVJ_TRY(thresh_count(ctx, H.h.ix, &H.dp.s, opts, &H.dthr, nullptr, true, plan, &total));
+    if (total == 0) return IVJ_OK;
+    if (!host_result_fits((size_t)total * 8))
+        return fail(IVJ_ENOMEM, "the result (" + std::to_string(total) + " pairs, " + std::to_string((size_t)total * 8 >> 20) + " MiB) does not fit the available host memory; use ivj_overlap_thresh_dev");
+    DevBuf op, ob;
+    hipError_t e = hipMalloc(&op.p, (size_t)total * 4);
+    if (e == hipSuccess) e = hipMalloc(&ob.p, (size_t)total * 4);
+    if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(pairs): ") + hipGetErrorString(e));
+    IVJ_TRY(thresh_emit(ctx, H.h.ix, plan, (int32_t*)op.p, (int32_t*)ob.p));
+    out->probe_idx = (int32_t*)host_result_alloc((size_t)total * 4);
+    out->build_idx = (int32_t*)host_result_alloc((size_t)total * 4);
+    if (!out->probe_idx || !out->build_idx) { ivj_pairs_free(out); return fail(IVJ_ENOMEM, "host malloc(pairs)"); }
+    HostXfer copy(ctx->stream, &ctx->xfer);
+    copy.d2h(out->probe_idx, op.p, (size_t)total * 4);
+    copy.d2h(out->build_idx, ob.p, (size_t)total * 4);
+    const hipError_t ce = copy.finish();
+    if (ce != hipSuccess) { ivj_pairs_free(out); return fail(IVJ_EHIP, std::string("D2H(pairs): ") + hipGetErrorString(ce)); }
+    out->n_pairs = total;
+    return IVJ_OK;
+} IVJ_ABI_CATCH
+
+int ivj_count_overlaps_thresh(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, const ivj_thresholds* thr,
+                              int64_t* counts) try {
+    if (!ctx) return fail(IVJ_EINVAL, "ctx is NULL");
+    IVJ_TRY(check_opts(opts));
+    IVJ_TRY(check_side(probe, "probe"));
+    IVJ_TRY(check_side(build, "build"));
+    IVJ_TRY(check_thresholds(thr));
+    if (probe->n == 0) return IVJ_OK;
+    if (!counts) return fail(IVJ_EINVAL, "counts is NULL");
+    DeviceGuard g(ctx->device);
+    ThreshHost H;
+    IVJ_TRY(thresh_upload(ctx, probe, build, opts, thr, H));
+    DevBuf dc;
+    hipError_t e = hipMalloc(&dc.p, (size_t)probe->n * 8);
+    if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(counts): ") + hipGetErrorString(e));
+    ThreshPlan plan;
+    IVJ_TRY(thresh_count(ctx, H.h.ix, &H.dp.s, opts, &H.dthr, (int64_t*)dc.p, false, plan, nullptr));
     HostXfer copy(ctx->stream, &ctx->xfer);
     copy.d2h(counts, dc.p, (size_t)probe->n * 8);
     HIP_TRY(copy.finish());

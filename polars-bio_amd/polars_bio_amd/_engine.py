@@ -29,6 +29,7 @@ ABI_SYMBOLS = [
     "ivj_overlap", "ivj_pairs_free", "ivj_count_overlaps", "ivj_nearest",
     "ivj_index_build_dev", "ivj_index_free", "ivj_overlap_count_dev", "ivj_overlap_fill_dev", "ivj_overlap_fused_dev",
     "ivj_count_overlaps_dev", "ivj_nearest_dev",
+    "ivj_overlap_thresh", "ivj_count_overlaps_thresh", "ivj_overlap_thresh_dev", "ivj_count_overlaps_thresh_dev",
     "ivj_side_from_arrow", "ivj_materialize_dev", "ivj_overlap_fused_rows_dev", "ivj_take_dev", "ivj_take", "ivj_overlap_rows", "ivj_rows_free", "ivj_rows_export_arrow",
     "ivj_subtract", "ivj_complement", "ivj_pieces_free", "ivj_subtract_dev",
     "ivj_merge", "ivj_merged_free", "ivj_cluster", "ivj_coverage", "ivj_cluster_dev", "ivj_merge_dev", "ivj_coverage_dev",
@@ -67,6 +68,9 @@ ROW_COLUMNS = ("probe_idx", "build_idx", "contig", "start_1", "end_1", "start_2"
 
 IVJ_ECAPACITY, IVJ_ESTATE, IVJ_EPEER = -4, -5, -6
 
+# ivj_thresholds minima (include/ivjoin.h): uint32 base counts, 0 = no requirement, THRESH_NEVER = the row never matches
+THRESH_NEVER = 0xFFFFFFFF
+
 
 class EngineError(RuntimeError):
     """HIP / engine failure (the reference surfaces these as PanicException).  ``code`` = the IVJ_E* status."""
@@ -98,6 +102,10 @@ class _Opts(C.Structure):
     _fields_ = [("filter_op", C.c_int32), ("n_contigs", C.c_int32), ("nearest_k", C.c_int32),
                 ("include_overlaps", C.c_int32), ("partition_mode", C.c_int32), ("table_mode", C.c_int32), ("slice_rows", C.c_int32), ("slice_chunk", C.c_int32),
                 ("deterministic", C.c_int32), ("nearest_ignore", C.c_int32)]
+
+
+class _Thresholds(C.Structure):
+    _fields_ = [("min_overlap", C.c_uint32), ("probe_min", C.c_void_p), ("build_min", C.c_void_p)]
 
 
 class _Pairs(C.Structure):
@@ -199,6 +207,11 @@ def load_library() -> C.CDLL:
         L.ivj_overlap_fused_dev.argtypes = [vp, vp, P, O, vp, vp, C.c_int64, C.POINTER(C.c_int64)]
         L.ivj_count_overlaps_dev.argtypes = [vp, vp, P, O, vp]
         L.ivj_nearest_dev.argtypes = [vp, vp, P, O, vp, vp, vp]
+        T = C.POINTER(_Thresholds)
+        L.ivj_overlap_thresh.argtypes = [vp, P, P, O, T, C.POINTER(_Pairs)]
+        L.ivj_count_overlaps_thresh.argtypes = [vp, P, P, O, T, vp]
+        L.ivj_overlap_thresh_dev.argtypes = [vp, vp, P, O, T, vp, vp, C.c_int64, C.POINTER(C.c_int64)]
+        L.ivj_count_overlaps_thresh_dev.argtypes = [vp, vp, P, O, T, vp]
         L.ivj_materialize_dev.argtypes = [vp, P, P, C.POINTER(_Rows)]
         L.ivj_overlap_fused_rows_dev.argtypes = [vp, vp, P, O, C.POINTER(_Rows), C.POINTER(C.c_int64)]
         L.ivj_take_dev.argtypes = [vp, vp, C.c_int32, vp, C.c_int64, vp, vp]
@@ -333,6 +346,23 @@ def _ignore_mask(mask) -> int:
     if mask < 0 or mask > (NEAREST_IGNORE_LEFT | NEAREST_IGNORE_RIGHT):
         raise ValueError(f"nearest_ignore must be 0 or a mask of NEAREST_IGNORE_LEFT (1) and NEAREST_IGNORE_RIGHT (2), got {mask}")
     return mask
+
+
+def _u32_min(a, n: int, what: str):
+    """A column of per-row minima (ivj_thresholds) as contiguous uint32, or None."""
+    if a is None:
+        return None
+    a = np.ascontiguousarray(a, dtype=np.uint32)
+    if a.shape != (n,):
+        raise ValueError(f"{what} must hold one uint32 per row ({n}), got shape {a.shape}")
+    return a
+
+
+def make_thresholds(min_overlap: int = 0, probe_min_ptr: int = 0, build_min_ptr: int = 0) -> _Thresholds:
+    """ivj_thresholds from a scalar and two (host or device) addresses; 0 = not set."""
+    if not 0 <= int(min_overlap) <= THRESH_NEVER:
+        raise ValueError(f"min_overlap must fit uint32, got {min_overlap}")
+    return _Thresholds(int(min_overlap), probe_min_ptr or None, build_min_ptr or None)
 
 
 def _setop_code(op) -> int:
@@ -790,6 +820,42 @@ class Engine:
         del keep_p, keep_b
         return counts
 
+    def _host_thresholds(self, ps, bs, min_overlap, probe_min, build_min):
+        pm, bm = _u32_min(probe_min, ps.n, "probe_min"), _u32_min(build_min, bs.n, "build_min")
+        t = make_thresholds(min_overlap, pm.ctypes.data if pm is not None else 0, bm.ctypes.data if bm is not None else 0)
+        return t, (pm, bm)
+
+    def overlap_thresh(self, probe, build, strict: bool, n_contigs: int, min_overlap: int = 0, probe_min=None, build_min=None,
+                       partition_mode: int = 0):
+        """pb.overlap with overlap thresholds (ivj_overlap_thresh): the pairs with ov >= max(1, min_overlap, probe_min[probe row],
+        build_min[build row]); the minima are uint32 base counts per row (0 none, THRESH_NEVER never) -> (probe_idx, build_idx)."""
+        ps, keep_p = _host_side(*probe)
+        bs, keep_b = _host_side(*build)
+        t, keep_t = self._host_thresholds(ps, bs, min_overlap, probe_min, build_min)
+        o = make_opts(strict, n_contigs, partition_mode=partition_mode)
+        out = _Pairs()
+        _check(self.L, self.L.ivj_overlap_thresh(self.h, C.byref(ps), C.byref(bs), C.byref(o), C.byref(t), C.byref(out)), "ivj_overlap_thresh")
+        del keep_p, keep_b, keep_t
+        n = out.n_pairs
+        if n == 0:
+            self.L.ivj_pairs_free(C.byref(out))
+            return np.empty(0, np.int32), np.empty(0, np.int32)
+        owner = _PairsOwner(load_library(), out)
+        return _owned_view(out.probe_idx, n, owner), _owned_view(out.build_idx, n, owner)
+
+    def count_overlaps_thresh(self, probe, build, strict: bool, n_contigs: int, min_overlap: int = 0, probe_min=None, build_min=None,
+                              partition_mode: int = 0) -> np.ndarray:
+        """pb.count_overlaps with overlap thresholds (ivj_count_overlaps_thresh): int64 per probe row, probe order kept."""
+        ps, keep_p = _host_side(*probe)
+        bs, keep_b = _host_side(*build)
+        t, keep_t = self._host_thresholds(ps, bs, min_overlap, probe_min, build_min)
+        o = make_opts(strict, n_contigs, partition_mode=partition_mode)
+        counts = np.zeros(ps.n, np.int64)
+        _check(self.L, self.L.ivj_count_overlaps_thresh(self.h, C.byref(ps), C.byref(bs), C.byref(o), C.byref(t), counts.ctypes.data),
+               "ivj_count_overlaps_thresh")
+        del keep_p, keep_b, keep_t
+        return counts
+
     def nearest(self, probe, build, strict: bool, n_contigs: int, k: int = 1, include_overlaps: bool = True,
                 table_mode: int = 0, partition_mode: int = 0, nearest_ignore: int = 0):
         """partition_mode 0 auto / 1 bucket the probe side first / 2 never: same result, probe order kept.
@@ -866,6 +932,22 @@ class Engine:
             return n.value, False
         _check(self.L, rc, "ivj_overlap_fused_dev")
         return n.value, True
+
+    def overlap_thresh_dev(self, ix: DeviceIndex, probe: _Side, opts: _Opts, thr: _Thresholds, probe_idx_ptr: int, build_idx_ptr: int,
+                           capacity: int):
+        """Thresholded join on an index (ivj_overlap_thresh_dev; thr from make_thresholds with device addresses) -> (n_pairs, fits).
+        fits=False: nothing was written, grow the buffers to n_pairs.  Null buffers with capacity 0 count only."""
+        n = C.c_int64(0)
+        rc = self.L.ivj_overlap_thresh_dev(self.h, ix.handle, C.byref(probe), C.byref(opts), C.byref(thr), C.c_void_p(probe_idx_ptr or None),
+                                           C.c_void_p(build_idx_ptr or None), capacity, C.byref(n))
+        if rc == IVJ_ECAPACITY:
+            return n.value, False
+        _check(self.L, rc, "ivj_overlap_thresh_dev")
+        return n.value, True
+
+    def count_overlaps_thresh_dev(self, ix: DeviceIndex, probe: _Side, opts: _Opts, thr: _Thresholds, counts_ptr: int):
+        _check(self.L, self.L.ivj_count_overlaps_thresh_dev(self.h, ix.handle, C.byref(probe), C.byref(opts), C.byref(thr),
+                                                            C.c_void_p(counts_ptr)), "ivj_count_overlaps_thresh_dev")
 
     def materialize_dev(self, probe: _Side, build: _Side, n_pairs: int, probe_idx_ptr: int, build_idx_ptr: int,
                         contig_ptr: int = 0, start_1_ptr: int = 0, end_1_ptr: int = 0, start_2_ptr: int = 0, end_2_ptr: int = 0):

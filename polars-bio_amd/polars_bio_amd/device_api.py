@@ -15,7 +15,7 @@ import torch  # noqa: F401  (must precede the dlopen of libivjoin_hip.so in this
 
 from typing import Optional, Tuple
 
-from ._engine import MULTI_CONSENSUS, MULTI_SEGMENTS, DeviceIndex, Engine, check_multi, make_opts
+from ._engine import MULTI_CONSENSUS, MULTI_SEGMENTS, DeviceIndex, Engine, check_multi, make_opts, make_thresholds
 
 
 class DeviceSide:
@@ -160,6 +160,70 @@ class DeviceJoin:
         try:
             out = torch.empty(probe.n, dtype=torch.int64, device=probe.start.device)
             self.engine.count_overlaps_dev(ix, probe.as_c(), opts, out.data_ptr())
+        finally:
+            if own:
+                ix.close()
+        return out
+
+    # ---- overlap thresholds (include/ivjoin.h: ivj_thresholds) ---------------------------------------
+    def _thresholds(self, probe: DeviceSide, build: DeviceSide, min_overlap: int, probe_min, build_min):
+        """probe_min / build_min: contiguous CUDA tensors of one 4-byte unsigned base count per row (torch.uint32, or torch.int32
+        holding the same bits: -1 = never), or None."""
+        torch = self.torch
+        for t, side, what in ((probe_min, probe, "probe_min"), (build_min, build, "build_min")):
+            if t is None:
+                continue
+            if t.dtype not in (torch.int32, torch.uint32) or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (side.n,):
+                raise ValueError(f"{what} must be a contiguous 4-byte integer CUDA tensor with one element per row")
+        if not min_overlap and probe_min is None and build_min is None:
+            raise ValueError("no threshold is set: use overlap / count_overlaps")
+        return make_thresholds(min_overlap, probe_min.data_ptr() if probe_min is not None and probe.n else 0,
+                               build_min.data_ptr() if build_min is not None and build.n else 0)
+
+    def overlap_thresh(self, probe: DeviceSide, build: DeviceSide, strict: bool, n_contigs: int, min_overlap: int = 0, probe_min=None,
+                       build_min=None, index=None, out=None, partition_mode: int = 0):
+        """Thresholded join (ivj_overlap_thresh_dev): the pairs with ov >= max(1, min_overlap, probe_min[probe row],
+        build_min[build row]) -> (probe_idx, build_idx) int32 tensors.  ``out``: optional pair of preallocated int32 CUDA tensors,
+        used when they hold the result (views of their first n_pairs elements come back)."""
+        torch = self.torch
+        opts = make_opts(strict, n_contigs, partition_mode=partition_mode)
+        thr = self._thresholds(probe, build, min_overlap, probe_min, build_min)
+        if probe.n == 0 or build.n == 0:
+            e = torch.empty(0, dtype=torch.int32, device=probe.start.device)
+            return e, e.clone()
+        own = index is None
+        ix = self.engine.index_build_dev(build.as_c(), opts, False) if own else index
+        try:
+            side = probe.as_c()
+            if out is not None:
+                total, fits = self.engine.overlap_thresh_dev(ix, side, opts, thr, out[0].data_ptr(), out[1].data_ptr(),
+                                                             min(out[0].numel(), out[1].numel()))
+                if fits:
+                    return out[0][:total], out[1][:total]
+            else:
+                total, _ = self.engine.overlap_thresh_dev(ix, side, opts, thr, 0, 0, 0)
+            out_p = torch.empty(total, dtype=torch.int32, device=probe.start.device)
+            out_b = torch.empty(total, dtype=torch.int32, device=probe.start.device)
+            if total:
+                self.engine.overlap_thresh_dev(ix, side, opts, thr, out_p.data_ptr(), out_b.data_ptr(), total)
+        finally:
+            if own:
+                ix.close()
+        return out_p, out_b
+
+    def count_overlaps_thresh(self, probe: DeviceSide, build: DeviceSide, strict: bool, n_contigs: int, min_overlap: int = 0,
+                              probe_min=None, build_min=None, index=None, partition_mode: int = 0):
+        """Thresholded count (ivj_count_overlaps_thresh_dev) -> int64 tensor, probe order kept."""
+        torch = self.torch
+        opts = make_opts(strict, n_contigs, partition_mode=partition_mode)
+        thr = self._thresholds(probe, build, min_overlap, probe_min, build_min)
+        out = torch.zeros(probe.n, dtype=torch.int64, device=probe.start.device)
+        if probe.n == 0 or build.n == 0:
+            return out
+        own = index is None
+        ix = self.engine.index_build_dev(build.as_c(), opts, False) if own else index
+        try:
+            self.engine.count_overlaps_thresh_dev(ix, probe.as_c(), opts, thr, out.data_ptr())
         finally:
             if own:
                 ix.close()

@@ -4,6 +4,7 @@ The reference registers it on polars LazyFrames (/root/reference/polars_bio/pola
 range operations).  Here one accessor class is generated from the table below and registered on every frame library that
 is importable: polars LazyFrame / DataFrame (``pl.api.register_*_namespace``) and pandas DataFrame
 (``pd.api.extensions.register_dataframe_accessor``); the default output kind follows the frame the call was made on.
+Every keyword is passed through as given, the keyword-only ones included (``df.pb.overlap(other, min_frac1=0.5)``).
 """
 from __future__ import annotations
 

@@ -389,6 +389,91 @@ def _polars_lazy_result(df1, df2, zero_based, limit, batches_fn, **kw):
     return set_coordinate_system(PL.range_lazy_scan(make, schema), zero_based)
 
 
+# ---- overlap thresholds (include/ivjoin.h: ivj_thresholds) -------------------------------------------------------
+
+THRESH_NEVER = 0xFFFFFFFF      # the per-row minimum of a row that can never match
+
+
+def _validate_overlap_thresholds(min_overlap, min_frac1, min_frac2):
+    """-> (min_overlap as int or 0, min_frac1, min_frac2 as float or None).  ValueError: a min_overlap that is not an int >= 1
+    (bools are refused), a fraction outside (0, 1] or NaN."""
+    if min_overlap is None:
+        mo = 0
+    else:
+        if isinstance(min_overlap, (bool, np.bool_)) or not isinstance(min_overlap, (int, np.integer)):
+            raise ValueError(f"min_overlap must be an int >= 1, got {min_overlap!r}")
+        if min_overlap < 1:
+            raise ValueError(f"min_overlap must be >= 1, got {min_overlap}")
+        mo = min(int(min_overlap), THRESH_NEVER)           # minima are uint32: 2^32 - 1 and above read as "never" (see min_bases)
+    fr = []
+    for name, f in (("min_frac1", min_frac1), ("min_frac2", min_frac2)):
+        if f is None:
+            fr.append(None)
+            continue
+        if isinstance(f, (bool, np.bool_)) or not isinstance(f, (int, float, np.integer, np.floating)):
+            raise ValueError(f"{name} must be a float in (0, 1], got {f!r}")
+        f = float(f)
+        if not (f > 0.0 and f <= 1.0):                     # NaN fails both comparisons
+            raise ValueError(f"{name} must be in (0, 1], got {f}")
+        fr.append(f)
+    return mo, fr[0], fr[1]
+
+
+def min_bases(length, frac: float) -> np.ndarray:
+    """Per-row minimum base count of a fractional overlap threshold: m(r) = the smallest integer m >= 1 with
+    m / len(r) >= frac evaluated in IEEE float64, as uint32; THRESH_NEVER for rows with len <= 0.  ``length``: int64 lengths.
+    Computed as ceil(frac * len) and corrected by one in either direction with the literal division test; float64 division is
+    monotone in m, so one step each way suffices -- asserted."""
+    length = np.asarray(length, dtype=np.int64)
+    out = np.full(length.shape, THRESH_NEVER, dtype=np.uint32)
+    ok = length > 0
+    ln = length[ok]
+    lf = ln.astype(np.float64)
+    m = np.maximum(np.ceil(frac * lf).astype(np.int64), 1)
+    m = np.minimum(m, ln)                                  # frac <= 1: m = len always passes (len / len = 1.0)
+    up = (m.astype(np.float64) / lf) < frac                # the product rounded down: one more base
+    m = m + up
+    down = (m > 1) & (((m - 1).astype(np.float64) / lf) >= frac)   # the product rounded up: one base fewer still passes
+    m = m - down
+    assert ((m.astype(np.float64) / lf) >= frac).all() and ((m == 1) | (((m - 1).astype(np.float64) / lf) < frac)).all(), \
+        "min_bases: one correction step did not reach the smallest passing count"
+    assert (m >= 1).all() and (m <= ln).all()
+    # minima are uint32 and 2^32 - 1 is "never": a minimum that large (a row spanning all but a few of the 2^32 int32 positions)
+    # is stored as never
+    out[ok] = np.minimum(m, THRESH_NEVER).astype(np.uint32)
+    return out
+
+
+def _side_lengths(side, zero_based: bool) -> np.ndarray:
+    """len(r) of the semantics: end - start, + 1 for 1-based closed frames (int64)."""
+    return side[2].astype(np.int64) - side[1].astype(np.int64) + (0 if zero_based else 1)
+
+
+def _threshold_engine():
+    eng = default_engine()
+    if not hasattr(eng, "overlap_thresh") or not hasattr(eng, "count_overlaps_thresh"):
+        raise NotImplementedError(f"min_overlap / min_frac1 / min_frac2 need a single-device engine; the default engine is a "
+                                  f"{type(eng).__name__} (several devices), which has no thresholded join")
+    return eng
+
+
+def _threshold_minima(probe, build, zero_based, min_frac1, min_frac2):
+    pm = min_bases(_side_lengths(probe, zero_based), min_frac1) if min_frac1 is not None else None
+    bm = min_bases(_side_lengths(build, zero_based), min_frac2) if min_frac2 is not None else None
+    return pm, bm
+
+
+def _finish_eager(table, output_type, zero_based, limit):
+    """An eagerly computed result as the requested output kind: ``limit`` takes its head, a RecordBatchReader reads it."""
+    if limit is not None:
+        table = table.slice(0, max(int(limit), 0))
+    if output_type == "pyarrow.RecordBatchReader":
+        from ._metadata import set_coordinate_system
+        table = set_coordinate_system(A._decode_object_dict(table), zero_based)
+        return pa.RecordBatchReader.from_batches(table.schema, table.to_batches())
+    return A.from_arrow(table, output_type, zero_based)
+
+
 def _prepare(df1, df2, cols1, cols2, on_cols=None):
     """-> (t1, t2, probe, build, n_contigs, keys).  With on_cols the sides carry GROUP ids over (chrom, on values) as contig and
     n_contigs is the number of groups (ivj_host_group_ids); keys keeps the per-row chrom ids (the result's chrom columns) and, as
@@ -425,6 +510,10 @@ def overlap(
     read_options2=None,
     projection_pushdown: bool = True,
     limit: Union[int, None] = None,
+    *,
+    min_overlap: Union[int, None] = None,
+    min_frac1: Union[float, None] = None,
+    min_frac2: Union[float, None] = None,
 ):
     """Find pairs of overlapping genomic intervals (reference: range_op.py:117-256).
 
@@ -440,7 +529,24 @@ def overlap(
     (src/operation.rs:224-233, 294-298).
 
     ``on_cols``: further columns both frames must agree on (e.g. ``["strand"]``): pairs are formed within groups of equal
-    (chrom, on values) only; a null on-value matches nothing, like a null chrom."""
+    (chrom, on values) only; a null on-value matches nothing, like a null chrom.
+
+    Overlap thresholds (keyword-only; bedtools ``intersect -f / -F / -r`` and a minimum base count).  With
+    ``ov = min(end1, end2) - max(start1, start2)`` and ``len = end - start`` for 0-based half-open frames (both + 1 for 1-based
+    closed frames): ``min_overlap`` (int >= 1) keeps a pair iff ``ov >= min_overlap``; ``min_frac1`` (float in (0, 1]) iff
+    ``ov >= 1`` and ``ov / len(df1 row) >= min_frac1``, the division evaluated in IEEE float64 (``-f``); ``min_frac2`` the same
+    against the df2 row (``-F``; both equal is ``-r``).  All thresholds that are set must hold; an "either fraction suffices"
+    mode (``-e``) is not offered.  Any threshold implies ``ov >= 1``: rows that cover no position (zero-length, start > end),
+    intervals that only touch, and rows with a null chrom or on-value never match.  The fractions become per-row minimum base
+    counts on the host (``min_bases``); the device tests ``ov >= max(min_overlap, m1[df1 row], m2[df2 row])`` on every candidate
+    pair, so nothing is materialised only to be filtered.  ``on_cols``, ``overlap_output``, ``distinct_output`` and ``suffixes``
+    behave as without thresholds.  A thresholded call is EAGER whatever the ``output_type``: the finished table is converted,
+    ``limit`` takes its head, and ``pyarrow.RecordBatchReader`` is a reader over it; ``low_memory`` is not applied.  The streaming
+    entries (``overlap_batches``) and a multi-device default engine take no thresholds (the latter raises NotImplementedError).
+    Invalid thresholds raise ValueError."""
+    if min_overlap is not None or min_frac1 is not None or min_frac2 is not None:
+        return _overlap_thresholded(df1, df2, suffixes, on_cols, cols1, cols2, overlap_output, distinct_output, output_type, limit,
+                                    min_overlap, min_frac1, min_frac2)
     on_cols = _validate_overlap_input(cols1, cols2, on_cols, suffixes, output_type)
     _check_on_cols_present(on_cols, df1, df2)
     zero_based = validate_coordinate_systems(df1, df2)
@@ -475,6 +581,20 @@ def overlap(
     else:
         p_idx, b_idx = default_engine().overlap(probe, build, strict=zero_based, n_contigs=n_contigs)
     return A.from_arrow(_assemble_overlap(t1, t2, p_idx, b_idx, mode, distinct_output, suffixes, keys), output_type, zero_based)
+
+
+def _overlap_thresholded(df1, df2, suffixes, on_cols, cols1, cols2, overlap_output, distinct_output, output_type, limit,
+                         min_overlap, min_frac1, min_frac2):
+    mo, f1, f2 = _validate_overlap_thresholds(min_overlap, min_frac1, min_frac2)
+    on_cols = _validate_overlap_input(cols1, cols2, on_cols, suffixes, output_type)
+    _check_on_cols_present(on_cols, df1, df2)
+    zero_based = validate_coordinate_systems(df1, df2)
+    mode = _parse_overlap_output_mode(overlap_output)
+    eng = _threshold_engine()
+    t1, t2, probe, build, n_contigs, keys = _prepare(df1, df2, cols1, cols2, on_cols)
+    pm, bm = _threshold_minima(probe, build, zero_based, f1, f2)
+    p_idx, b_idx = eng.overlap_thresh(probe, build, strict=zero_based, n_contigs=n_contigs, min_overlap=mo, probe_min=pm, build_min=bm)
+    return _finish_eager(_assemble_overlap(t1, t2, p_idx, b_idx, mode, distinct_output, suffixes, keys), output_type, zero_based, limit)
 
 
 def nearest(
@@ -546,6 +666,10 @@ def count_overlaps(
     naive_query: bool = True,
     projection_pushdown: bool = True,
     limit: Union[int, None] = None,
+    *,
+    min_overlap: Union[int, None] = None,
+    min_frac1: Union[float, None] = None,
+    min_frac2: Union[float, None] = None,
 ):
     """Count the df2 intervals overlapping every df1 interval (reference: range_op.py:418-597).
     Output = df1 columns + ``count`` (Int64), df1 row order kept
@@ -553,7 +677,24 @@ def count_overlaps(
     reference's SQL sweep (range_op.py:512-597), which computes the same two-rank formula the
     device kernel uses; both values run the same kernel here, the sweep's output naming
     (key columns + suffixes[0]) is honoured, followed by the ``on_cols`` (df1's values).  ``on_cols``: only df2 intervals of
-    the df1 row's group of equal (chrom, on values) are counted."""
+    the df1 row's group of equal (chrom, on values) are counted.
+
+    ``min_overlap`` / ``min_frac1`` / ``min_frac2`` (keyword-only): count only the df2 intervals that pass the overlap
+    thresholds -- the semantics, the float64 rule and the limits are those of ``overlap`` (which see); the count of a df1 row
+    equals the number of its rows in the thresholded ``overlap``.  The pairs are counted on the device, never enumerated.  A
+    thresholded call is eager whatever the ``output_type`` (``limit`` takes the head of the finished table,
+    ``pyarrow.RecordBatchReader`` reads it); ``count_overlaps_batches`` takes no thresholds."""
+    if min_overlap is not None or min_frac1 is not None or min_frac2 is not None:
+        mo, f1, f2 = _validate_overlap_thresholds(min_overlap, min_frac1, min_frac2)
+        on_cols = _validate_overlap_input(cols1, cols2, on_cols, suffixes, output_type)
+        _check_on_cols_present(on_cols, df1, df2)
+        zero_based = validate_coordinate_systems(df1, df2)
+        eng = _threshold_engine()
+        t1, t2, probe, build, n_contigs, _keys = _prepare(df1, df2, cols1, cols2, on_cols)
+        pm, bm = _threshold_minima(probe, build, zero_based, f1, f2)
+        counts = eng.count_overlaps_thresh(probe, build, strict=zero_based, n_contigs=n_contigs, min_overlap=mo, probe_min=pm, build_min=bm)
+        c1 = list(DEFAULT_INTERVAL_COLUMNS if cols1 is None else cols1)
+        return _finish_eager(_assemble_count(t1, counts, naive_query, c1, suffixes, on_cols), output_type, zero_based, limit)
     on_cols = _validate_overlap_input(cols1, cols2, on_cols, suffixes, output_type)
     _check_on_cols_present(on_cols, df1, df2)
     zero_based = validate_coordinate_systems(df1, df2)
