@@ -400,6 +400,57 @@ int ivj_coverage_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, con
  * an index without the end order is completed here.  partition_mode 1 buckets the probes first; 0 and 2 run in probe order. */
 int ivj_overlap_bases_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, const ivj_opts* opts, int64_t* bases_dev);
 
+/* ---- merge with aggregates: a value column reduced per merged interval (bedtools merge -c / -o) -----------------------------------
+ * ivj_merge plus, per value column, any of count / sum / min / max / mean over the rows merged into each interval.  The merged
+ * table is exactly ivj_merge's for the same input; n_cols value columns share one cluster sweep.  Per column and cluster, over the
+ * VALID values only (valid == NULL: all; otherwise valid[row] != 0):
+ *   count  int64 number of valid values
+ *   sum    int64 columns: accumulated as uint64, i.e. modulo 2^64 (the bits of a wrapping int64 sum); double columns: double.
+ *          0 where count == 0.  A NaN value makes the sum and the mean of its cluster NaN.
+ *   min / max   the column's type; doubles with fmin / fmax: NaN only where every valid value of the cluster is NaN
+ *   mean   (double)sum / (double)count with the sum above (read as int64); float64
+ * min, max and mean of a cluster with count == 0 are unspecified (the front door makes them nulls).
+ * Values are indexed by the row's position in the frame columns (host form: frame->row_id must be NULL); in the _dev form by the
+ * row the index reports (its side's row_id when it had one), and a row outside [0, n_values) contributes nothing, as if invalid.
+ * No atomics: integer results are bit-identical from run to run.  A double sum is evaluated in an order fixed by the sorted order
+ * of the index, and both index builds (the LSD sort and the balanced bucket build) keep rows of equal (contig, start) in input
+ * order, so double sums repeat bit for bit too, for the same input rows in the same order on the same library build.
+ * IVJ_EINVAL: n_cols outside [1, IVJ_MAX_AGG_COLS], ops == 0 or with unknown bits, an unknown dtype, NULL values with rows
+ * present, a NULL output column of an operation that was asked for (_dev form, once the result fits). */
+#define IVJ_AGG_SUM 1u
+#define IVJ_AGG_MIN 2u
+#define IVJ_AGG_MAX 4u
+#define IVJ_AGG_MEAN 8u
+#define IVJ_AGG_COUNT 16u
+#define IVJ_AGG_I64 0
+#define IVJ_AGG_F64 1
+#define IVJ_MAX_AGG_COLS 16
+typedef struct {
+    const void* values;      /* int64 or double, one per row */
+    const uint8_t* valid;    /* one byte per row, 1 = use the value; NULL = all valid */
+    int32_t dtype;           /* IVJ_AGG_I64 / IVJ_AGG_F64 */
+    uint32_t ops;            /* mask of IVJ_AGG_* */
+} ivj_agg_in;
+typedef struct {
+    void* sum;               /* int64 (wrapped) / double */
+    void* min;               /* the column's type */
+    void* max;
+    double* mean;
+    int64_t* count;          /* each: NULL where not asked for */
+} ivj_agg_out;
+
+/* Host form: out and agg_out[0 .. n_cols) receive library-owned buffers of out->n entries (only the operations asked for),
+ * released by ivj_merge_agg_free. */
+int ivj_merge_agg(ivj_ctx* ctx, const ivj_side* frame, const ivj_opts* opts, int64_t min_dist, int32_t n_cols,
+                  const ivj_agg_in* cols, ivj_merged* out, ivj_agg_out* agg_out);
+void ivj_merge_agg_free(ivj_merged* m, ivj_agg_out* agg_out, int32_t n_cols);
+/* Device form, the capacity protocol of ivj_merge_dev: *n_merged always receives the total; IVJ_ECAPACITY when it exceeds
+ * `capacity`, and nothing is written then.  cols[k].values / valid are device pointers to n_values elements; agg_out[k] holds
+ * the caller's device columns of `capacity` elements (operations not asked for are not written). */
+int ivj_merge_agg_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_opts* opts, int64_t min_dist, int64_t capacity, int32_t* contig_dev,
+                      int32_t* start_dev, int32_t* end_dev, int64_t* n_intervals_dev, int64_t n_values, int32_t n_cols,
+                      const ivj_agg_in* cols, const ivj_agg_out* agg_out, int64_t* n_merged);
+
 /* ---- depth: run-length coverage blocks of one frame ------------------------------------------------------------------------------
  * The disjoint maximal runs of positions covered by the same number (>= 1) of the frame's rows, in (contig id, start) order: the
  * block form (chrom, start, end, coverage) of the reference's pb.depth (polars_bio/pileup_op.py:94-100), computed from an interval

@@ -35,6 +35,7 @@
 #include "setop.hip.h"
 #include "multi.hip.h"
 #include "thresh.hip.h"
+#include "merge_agg.hip.h"
 
 using namespace ivj;
 
@@ -45,6 +46,7 @@ using namespace ivj;
 #include "host_cslice.hip.h"
 #include "host_join.hip.h"
 #include "host_sortscan.hip.h"
+#include "host_merge_agg.hip.h"
 #include "host_depth.hip.h"
 #include "host_depth_sum.hip.h"
 #include "host_depth_query.hip.h"
@@ -628,6 +630,117 @@ int ivj_merge(ivj_ctx* ctx, const ivj_side* side, const ivj_opts* opts, int64_t 
     copy.d2h(out->n_intervals, cnt, (size_t)cl.n * 8);
     const hipError_t e = copy.finish();
     if (e != hipSuccess) { ivj_merged_free(out); return fail(IVJ_EHIP, std::string("D2H(merged): ") + hipGetErrorString(e)); }
+    out->n = cl.n;
+    return IVJ_OK;
+} IVJ_ABI_CATCH
+
+// ---------------------------------------------------------------- merge with aggregates (merge_agg.hip.h)
+
+int ivj_merge_agg_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_opts* opts, int64_t min_dist, int64_t capacity, int32_t* contig_dev, int32_t* start_dev,
+                      int32_t* end_dev, int64_t* n_intervals_dev, int64_t n_values, int32_t n_cols, const ivj_agg_in* cols,
+                      const ivj_agg_out* agg_out, int64_t* n_merged) try {
+    if (!ctx || !ix || !n_merged) return fail(IVJ_EINVAL, "ctx, index or n_merged is NULL");
+    IVJ_TRY(check_opts(opts));
+    if (min_dist < 0 || capacity < 0 || n_values < 0) return fail(IVJ_EINVAL, "min_dist, capacity or n_values < 0");
+    IVJ_TRY(check_agg_cols(n_cols, cols, ix->n > 0 && n_values > 0));
+    DeviceGuard g(ctx->device);
+    Clusters cl;
+    IVJ_TRY(cluster_core(ctx, ix, opts->filter_op == IVJ_FILTER_STRICT, (long long)min_dist, merge_agg_bytes(ix->n), cl));
+    *n_merged = cl.n;
+    if (cl.n == 0) return IVJ_OK;
+    if (cl.n > capacity) return fail(IVJ_ECAPACITY, "merge output capacity " + std::to_string(capacity) + " < " + std::to_string(cl.n) + " intervals");
+    if (!contig_dev || !start_dev || !end_dev || !n_intervals_dev || !agg_out) return fail(IVJ_EINVAL, "merge output buffers are NULL");
+    IVJ_TRY(check_agg_outs(n_cols, cols, agg_out));
+    void* part = arena_take<AggState<double>>(ctx, 2 * magg_num_tiles(ix->n) + 1);
+    HIP_TRY(hipMemcpyAsync(contig_dev, cl.m_contig, (size_t)cl.n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(start_dev, cl.m_start, (size_t)cl.n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(end_dev, cl.m_end, (size_t)cl.n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    LAUNCH(ctx, "cluster_counts", k_cluster_counts, grid1d(cl.n, 256), 256, (const int32_t*)cl.m_first, cl.n, (long long*)n_intervals_dev);
+    for (int32_t k = 0; k < n_cols; ++k) IVJ_TRY(merge_agg_col(ctx, ix, cl, cols[k], n_values, agg_out[k], part));
+    HIP_TRY(hipGetLastError());
+    return IVJ_OK;
+} IVJ_ABI_CATCH
+
+void ivj_merge_agg_free(ivj_merged* m, ivj_agg_out* agg_out, int32_t n_cols) {
+    ivj_merged_free(m);
+    if (!agg_out) return;
+    for (int32_t k = 0; k < n_cols; ++k) {
+        std::free(agg_out[k].sum); std::free(agg_out[k].min); std::free(agg_out[k].max); std::free(agg_out[k].mean); std::free(agg_out[k].count);
+        std::memset(&agg_out[k], 0, sizeof(agg_out[k]));
+    }
+}
+
+int ivj_merge_agg(ivj_ctx* ctx, const ivj_side* side, const ivj_opts* opts, int64_t min_dist, int32_t n_cols, const ivj_agg_in* cols,
+                  ivj_merged* out, ivj_agg_out* agg_out) try {
+    if (!ctx || !out || !agg_out) return fail(IVJ_EINVAL, "ctx, out or agg_out is NULL");
+    std::memset(out, 0, sizeof(*out));
+    if (n_cols >= 1 && n_cols <= IVJ_MAX_AGG_COLS) std::memset(agg_out, 0, sizeof(*agg_out) * (size_t)n_cols);
+    IVJ_TRY(check_opts(opts));
+    IVJ_TRY(check_side(side, "frame"));
+    if (min_dist < 0) return fail(IVJ_EINVAL, "min_dist < 0");
+    IVJ_TRY(check_agg_cols(n_cols, cols, side->n > 0));
+    if (side->row_id) return fail(IVJ_EINVAL, "ivj_merge_agg reads the values by frame position: row_id must be NULL");
+    if (side->n == 0) return IVJ_OK;
+    const int64_t n = side->n;
+    DeviceGuard g(ctx->device);
+    DevSide ds;
+    IVJ_TRY(upload_side(ctx, side, ds));
+    IndexHolder h;
+    IVJ_TRY(index_build(ctx, &ds.s, opts, 2, &h.ix));      // sweep only: no lookup tables
+    // arena: the count column, the tile parts, one value column with its validity bytes, the five result columns of one value column
+    const size_t col8 = align_up((size_t)(n + 1) * 8);
+    Clusters cl;
+    IVJ_TRY(cluster_core(ctx, h.ix, opts->filter_op == IVJ_FILTER_STRICT, (long long)min_dist,
+                         col8 + merge_agg_bytes(n) + col8 + align_up((size_t)n + 1) + 5 * col8, cl));
+    long long* cnt = arena_take<long long>(ctx, n + 1);
+    void* part = arena_take<AggState<double>>(ctx, 2 * magg_num_tiles(n) + 1);
+    long long* d_val = arena_take<long long>(ctx, n + 1);
+    uint8_t* d_valid = arena_take<uint8_t>(ctx, n + 1);
+    void* d_res[5];
+    for (int r = 0; r < 5; ++r) d_res[r] = arena_take<long long>(ctx, n + 1);
+    LAUNCH(ctx, "cluster_counts", k_cluster_counts, grid1d(cl.n, 256), 256, (const int32_t*)cl.m_first, cl.n, cnt);
+    const size_t m4 = (size_t)cl.n * 4, m8 = (size_t)cl.n * 8;
+    out->contig = (int32_t*)host_result_alloc(m4);
+    out->start = (int32_t*)host_result_alloc(m4);
+    out->end = (int32_t*)host_result_alloc(m4);
+    out->n_intervals = (int64_t*)host_result_alloc(m8);
+    bool alloc_ok = out->contig && out->start && out->end && out->n_intervals;
+    for (int32_t k = 0; k < n_cols && alloc_ok; ++k) {
+        const uint32_t ops = cols[k].ops;
+        ivj_agg_out& o = agg_out[k];
+        if (ops & IVJ_AGG_SUM) alloc_ok = alloc_ok && (o.sum = host_result_alloc(m8));
+        if (ops & IVJ_AGG_MIN) alloc_ok = alloc_ok && (o.min = host_result_alloc(m8));
+        if (ops & IVJ_AGG_MAX) alloc_ok = alloc_ok && (o.max = host_result_alloc(m8));
+        if (ops & IVJ_AGG_MEAN) alloc_ok = alloc_ok && (o.mean = (double*)host_result_alloc(m8));
+        if (ops & IVJ_AGG_COUNT) alloc_ok = alloc_ok && (o.count = (int64_t*)host_result_alloc(m8));
+    }
+    if (!alloc_ok) { ivj_merge_agg_free(out, agg_out, n_cols); return fail(IVJ_ENOMEM, "host malloc(merged aggregates)"); }
+    int rc = IVJ_OK;
+    hipError_t e = hipSuccess;
+    {
+        HostXfer copy(ctx->stream, &ctx->xfer);
+        copy.d2h(out->contig, cl.m_contig, m4);
+        copy.d2h(out->start, cl.m_start, m4);
+        copy.d2h(out->end, cl.m_end, m4);
+        copy.d2h(out->n_intervals, cnt, m8);
+        const ivj_agg_out dev{d_res[0], d_res[1], d_res[2], (double*)d_res[3], (int64_t*)d_res[4]};
+        for (int32_t k = 0; k < n_cols && rc == IVJ_OK; ++k) {
+            // the copies and the launches are ordered by the stream: column k + 1 overwrites the buffers after column k's copies left
+            copy.h2d(d_val, cols[k].values, (size_t)n * 8);
+            if (cols[k].valid) copy.h2d(d_valid, cols[k].valid, (size_t)n);
+            const ivj_agg_in in{d_val, cols[k].valid ? d_valid : nullptr, cols[k].dtype, cols[k].ops};
+            rc = merge_agg_col(ctx, h.ix, cl, in, n, dev, part);
+            const ivj_agg_out& o = agg_out[k];
+            if (o.sum) copy.d2h(o.sum, dev.sum, m8);
+            if (o.min) copy.d2h(o.min, dev.min, m8);
+            if (o.max) copy.d2h(o.max, dev.max, m8);
+            if (o.mean) copy.d2h(o.mean, dev.mean, m8);
+            if (o.count) copy.d2h(o.count, dev.count, m8);
+        }
+        e = copy.finish();
+    }
+    if (rc != IVJ_OK) { ivj_merge_agg_free(out, agg_out, n_cols); return rc; }
+    if (e != hipSuccess) { ivj_merge_agg_free(out, agg_out, n_cols); return fail(IVJ_EHIP, std::string("copies(merged aggregates): ") + hipGetErrorString(e)); }
     out->n = cl.n;
     return IVJ_OK;
 } IVJ_ABI_CATCH

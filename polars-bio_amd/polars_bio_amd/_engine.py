@@ -33,6 +33,7 @@ ABI_SYMBOLS = [
     "ivj_side_from_arrow", "ivj_materialize_dev", "ivj_overlap_fused_rows_dev", "ivj_take_dev", "ivj_take", "ivj_overlap_rows", "ivj_rows_free", "ivj_rows_export_arrow",
     "ivj_subtract", "ivj_complement", "ivj_pieces_free", "ivj_subtract_dev",
     "ivj_merge", "ivj_merged_free", "ivj_cluster", "ivj_coverage", "ivj_cluster_dev", "ivj_merge_dev", "ivj_coverage_dev",
+    "ivj_merge_agg", "ivj_merge_agg_free", "ivj_merge_agg_dev",
     "ivj_overlap_bases", "ivj_overlap_bases_dev",
     "ivj_depth", "ivj_blocks_free", "ivj_depth_dev", "ivj_depth_summary", "ivj_depth_summary_dev",
     "ivj_setop", "ivj_regions_free", "ivj_set_stats", "ivj_setop_dev", "ivj_set_stats_dev",
@@ -62,6 +63,12 @@ SETOPS = {"intersection": SETOP_INTERSECTION, "union": SETOP_UNION, "difference"
 # ivj_multi_inter / ivj_multi_inter_dev (include/ivjoin.h: IVJ_MAX_FRAMES, IVJ_MULTI_*)
 MAX_FRAMES = 64
 MULTI_SEGMENTS, MULTI_CONSENSUS = 0, 1
+
+# ivj_merge_agg / ivj_merge_agg_dev (include/ivjoin.h: IVJ_AGG_*, IVJ_MAX_AGG_COLS)
+AGG_SUM, AGG_MIN, AGG_MAX, AGG_MEAN, AGG_COUNT = 1, 2, 4, 8, 16
+AGG_OPS = {"sum": AGG_SUM, "min": AGG_MIN, "max": AGG_MAX, "mean": AGG_MEAN, "count": AGG_COUNT}
+AGG_I64, AGG_F64 = 0, 1
+MAX_AGG_COLS = 16
 
 ROW_COLUMNS = ("probe_idx", "build_idx", "contig", "start_1", "end_1", "start_2", "end_2")
 
@@ -120,6 +127,14 @@ class _Rows(C.Structure):
 class _Merged(C.Structure):
     _fields_ = [("n", C.c_int64), ("contig", C.POINTER(C.c_int32)), ("start", C.POINTER(C.c_int32)), ("end", C.POINTER(C.c_int32)),
                 ("n_intervals", C.POINTER(C.c_int64))]
+
+
+class _AggIn(C.Structure):
+    _fields_ = [("values", C.c_void_p), ("valid", C.c_void_p), ("dtype", C.c_int32), ("ops", C.c_uint32)]
+
+
+class _AggOut(C.Structure):
+    _fields_ = [("sum", C.c_void_p), ("min", C.c_void_p), ("max", C.c_void_p), ("mean", C.c_void_p), ("count", C.c_void_p)]
 
 
 class _Blocks(C.Structure):
@@ -233,6 +248,11 @@ def load_library() -> C.CDLL:
         L.ivj_coverage.argtypes = [vp, P, P, O, vp]
         L.ivj_cluster_dev.argtypes = [vp, vp, O, C.c_int64, vp, vp, vp, C.POINTER(C.c_int64)]
         L.ivj_merge_dev.argtypes = [vp, vp, O, C.c_int64, C.c_int64, vp, vp, vp, vp, C.POINTER(C.c_int64)]
+        L.ivj_merge_agg.argtypes = [vp, P, O, C.c_int64, C.c_int32, C.POINTER(_AggIn), C.POINTER(_Merged), C.POINTER(_AggOut)]
+        L.ivj_merge_agg_free.argtypes = [C.POINTER(_Merged), C.POINTER(_AggOut), C.c_int32]
+        L.ivj_merge_agg_free.restype = None
+        L.ivj_merge_agg_dev.argtypes = [vp, vp, O, C.c_int64, C.c_int64, vp, vp, vp, vp, C.c_int64, C.c_int32, C.POINTER(_AggIn),
+                                        C.POINTER(_AggOut), C.POINTER(C.c_int64)]
         L.ivj_depth.argtypes = [vp, P, O, C.POINTER(_Blocks)]
         L.ivj_blocks_free.argtypes = [C.POINTER(_Blocks)]
         L.ivj_blocks_free.restype = None
@@ -321,6 +341,37 @@ def _i32(a) -> np.ndarray:
     if a.dtype != np.int32 or not a.flags.c_contiguous:
         a = np.ascontiguousarray(a, dtype=np.int32)
     return a
+
+
+def agg_ops_mask(ops) -> int:
+    """A name or a list of names of AGG_OPS -> the mask of AGG_* (ValueError on an unknown name or an empty list).  An int is
+    taken as the mask itself and handed on unchecked: the library validates it."""
+    if isinstance(ops, (int, np.integer)) and not isinstance(ops, (bool, np.bool_)):
+        return int(ops) & 0xFFFFFFFF
+    names = [ops] if isinstance(ops, str) else list(ops)
+    if not names:
+        raise ValueError(f"no aggregate operation given: expected some of {sorted(AGG_OPS)}")
+    mask = 0
+    for name in names:
+        if not isinstance(name, str) or name not in AGG_OPS:
+            raise ValueError(f"unknown aggregate {name!r}: expected one of {sorted(AGG_OPS)}")
+        mask |= AGG_OPS[name]
+    return mask
+
+
+def _agg_column(values, valid, ops, n: int):
+    """One value column of merge_agg as the library reads it: contiguous int64 / float64 values, uint8 validity or None."""
+    values = np.asarray(values)
+    if values.dtype not in (np.int64, np.float64):
+        raise ValueError(f"value columns must be int64 or float64 arrays, got {values.dtype}")
+    values = np.ascontiguousarray(values)
+    if values.shape != (n,):
+        raise ValueError(f"a value column has shape {values.shape}, the frame has {n} rows")
+    if valid is not None:
+        valid = np.ascontiguousarray(np.asarray(valid).astype(bool, copy=False)).view(np.uint8)
+        if valid.shape != (n,):
+            raise ValueError(f"a validity column has shape {valid.shape}, the frame has {n} rows")
+    return values, valid, agg_ops_mask(ops)
 
 
 def _host_side(contig, start, end) -> Tuple[_Side, tuple]:
@@ -664,6 +715,48 @@ class Engine:
                     np.ctypeslib.as_array(out.end, shape=(n,)).copy(), np.ctypeslib.as_array(out.n_intervals, shape=(n,)).copy())
         finally:
             self.L.ivj_merged_free(C.byref(out))
+
+    def merge_agg(self, frame, strict: bool, n_contigs: int, agg, min_dist: int = 0):
+        """pb.merge(agg=...): ``agg`` = a list of (values, valid, ops) per value column -- values an int64 or float64 array with
+        one element per frame row (other dtypes are refused), valid a bool / uint8 array or None, ops a mask of AGG_* or a list
+        of names of AGG_OPS.  -> (contig id, start, end, n_intervals, [dict per column]); the dict maps each requested name
+        ("sum", "min", "max", "mean", "count") to its array: sum int64 (wrapped) / float64, min / max the column's type, mean
+        float64, count int64.  min / max / mean are unspecified where count is 0."""
+        fs, keep = _host_side(*frame)
+        o = make_opts(strict, n_contigs)
+        agg = list(agg)
+        cols = (_AggIn * max(len(agg), 1))()
+        outs = (_AggOut * max(len(agg), 1))()
+        dtypes = []
+        for k, (values, valid, ops) in enumerate(agg):
+            values, valid, ops = _agg_column(values, valid, ops, fs.n)
+            keep += (values, valid)
+            dtypes.append(values.dtype)
+            cols[k] = _AggIn(values.ctypes.data if fs.n else None, valid.ctypes.data if valid is not None and fs.n else None,
+                             AGG_I64 if values.dtype == np.int64 else AGG_F64, ops)
+        out = _Merged()
+        _check(self.L, self.L.ivj_merge_agg(self.h, C.byref(fs), C.byref(o), int(min_dist), len(agg), cols, C.byref(out), outs), "ivj_merge_agg")
+        del keep
+        try:
+            n = out.n
+
+            def column(ptr, dtype):
+                if n == 0:
+                    return np.empty(0, dtype)
+                return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_int64)), shape=(n,)).view(dtype).copy()
+
+            if n == 0:
+                table = (np.empty(0, np.int32), np.empty(0, np.int32), np.empty(0, np.int32), np.empty(0, np.int64))
+            else:
+                table = (np.ctypeslib.as_array(out.contig, shape=(n,)).copy(), np.ctypeslib.as_array(out.start, shape=(n,)).copy(),
+                         np.ctypeslib.as_array(out.end, shape=(n,)).copy(), np.ctypeslib.as_array(out.n_intervals, shape=(n,)).copy())
+            results = []
+            for k in range(len(agg)):
+                kinds = {"sum": dtypes[k], "min": dtypes[k], "max": dtypes[k], "mean": np.float64, "count": np.int64}
+                results.append({name: column(getattr(outs[k], name), kinds[name]) for name, bit in AGG_OPS.items() if cols[k].ops & bit})
+            return (*table, results)
+        finally:
+            self.L.ivj_merge_agg_free(C.byref(out), outs, len(agg))
 
     def depth(self, frame, strict: bool, n_contigs: int):
         """pb.depth: -> (contig id, start, end, depth) int32 arrays of the blocks of constant coverage >= 1, (contig id, start)
@@ -1009,6 +1102,26 @@ class Engine:
         if rc == -4:
             return n.value, False
         _check(self.L, rc, "ivj_merge_dev")
+        return n.value, True
+
+    def merge_agg_dev(self, ix: DeviceIndex, opts: _Opts, min_dist: int, capacity: int, contig_ptr: int, start_ptr: int, end_ptr: int,
+                      n_intervals_ptr: int, n_values: int, cols, outs):
+        """ivj_merge_agg_dev.  ``cols``: per value column (values_ptr, valid_ptr or 0, dtype AGG_I64 / AGG_F64, ops mask);
+        ``outs``: per value column a dict name -> device address of the caller's column (names of AGG_OPS; missing = NULL).
+        -> (n_merged, fits); fits=False: nothing was written, grow the buffers to n_merged."""
+        k = len(cols)
+        cin = (_AggIn * max(k, 1))()
+        cout = (_AggOut * max(k, 1))()
+        for i, (values_ptr, valid_ptr, dtype, ops) in enumerate(cols):
+            cin[i] = _AggIn(values_ptr or None, valid_ptr or None, int(dtype), int(ops))
+            cout[i] = _AggOut(*(outs[i].get(name) or None for name in ("sum", "min", "max", "mean", "count")))
+        n = C.c_int64(0)
+        rc = self.L.ivj_merge_agg_dev(self.h, ix.handle, C.byref(opts), int(min_dist), int(capacity), C.c_void_p(contig_ptr or None),
+                                      C.c_void_p(start_ptr or None), C.c_void_p(end_ptr or None), C.c_void_p(n_intervals_ptr or None),
+                                      int(n_values), k, cin, cout, C.byref(n))
+        if rc == IVJ_ECAPACITY:
+            return n.value, False
+        _check(self.L, rc, "ivj_merge_agg_dev")
         return n.value, True
 
     def depth_dev(self, ix: DeviceIndex, opts: _Opts, capacity: int, contig_ptr: int, start_ptr: int, end_ptr: int, depth_ptr: int):

@@ -15,7 +15,8 @@ import torch  # noqa: F401  (must precede the dlopen of libivjoin_hip.so in this
 
 from typing import Optional, Tuple
 
-from ._engine import MULTI_CONSENSUS, MULTI_SEGMENTS, DeviceIndex, Engine, check_multi, make_opts, make_thresholds
+from ._engine import (AGG_F64, AGG_I64, AGG_OPS, MULTI_CONSENSUS, MULTI_SEGMENTS, DeviceIndex, Engine, agg_ops_mask, check_multi, make_opts,
+                      make_thresholds)
 
 
 class DeviceSide:
@@ -285,22 +286,55 @@ class DeviceJoin:
                 ix.close()
         return md, bg
 
-    def merge(self, frame: DeviceSide, strict: bool, n_contigs: int, min_dist: int = 0, out=None):
+    def merge(self, frame: DeviceSide, strict: bool, n_contigs: int, min_dist: int = 0, out=None, agg=None):
         """Merged intervals of one frame -> (contig, start, end int32, n_intervals int64) tensors.
-        ``out``: optional preallocated 4-tuple (views of the first n_merged elements are returned)."""
+        ``out``: optional preallocated 4-tuple (views of the first n_merged elements are returned).
+        ``agg``: a list of (values, valid, ops) per value column -- values a contiguous int64 or float64 CUDA tensor indexed by
+        the frame's rows (by ``row_id`` where the frame carries one), valid a contiguous bool / uint8 CUDA tensor of the same
+        length or None, ops a name or list of names of "sum", "min", "max", "mean", "count" (or a mask of _engine.AGG_*).  The
+        result is then the 4-tuple plus one list with a dict per column, name -> tensor of n_merged elements: sum int64
+        (wrapped) / float64, min / max the column's type, mean float64, count int64; min / max / mean are unspecified where
+        count is 0."""
         torch = self.torch
         opts = make_opts(strict, n_contigs)
+        dev = frame.start.device
+        cols, n_values = [], 0
+        if agg is not None:
+            agg = list(agg)
+            for values, valid, ops in agg:
+                if values.dtype not in (torch.int64, torch.float64) or not values.is_cuda or not values.is_contiguous() or values.dim() != 1:
+                    raise ValueError("value columns must be contiguous 1-D int64 or float64 CUDA tensors")
+                if valid is not None and (valid.dtype not in (torch.bool, torch.uint8) or not valid.is_cuda or not valid.is_contiguous()
+                                          or valid.shape != values.shape):
+                    raise ValueError("validity columns must be contiguous bool / uint8 CUDA tensors of the value column's length")
+                cols.append((values, valid, AGG_I64 if values.dtype == torch.int64 else AGG_F64, agg_ops_mask(ops)))
+            lengths = {int(v.shape[0]) for v, _, _, _ in cols}
+            if len(lengths) > 1:
+                raise ValueError(f"the value columns of one call must have one length, got {sorted(lengths)}")
+            n_values = lengths.pop() if lengths else 0
         ix = self.engine.index_build_dev(frame.as_c(), opts, False, sweep_only=True)
         try:
             if out is None:
-                dev = frame.start.device
                 out = tuple(torch.empty(frame.n, dtype=dt, device=dev) for dt in (torch.int32, torch.int32, torch.int32, torch.int64))
-            n, fits = self.engine.merge_dev(ix, opts, min_dist, min(int(t.numel()) for t in out), *(t.data_ptr() for t in out))
+            cap = min(int(t.numel()) for t in out)
+            if agg is None:
+                n, fits = self.engine.merge_dev(ix, opts, min_dist, cap, *(t.data_ptr() for t in out))
+            else:
+                kinds = {"sum": None, "min": None, "max": None, "mean": torch.float64, "count": torch.int64}
+                results = [{name: torch.empty(cap, dtype=kinds[name] or values.dtype, device=dev) for name, bit in AGG_OPS.items() if ops & bit}
+                           for values, _, _, ops in cols]
+                n, fits = self.engine.merge_agg_dev(
+                    ix, opts, min_dist, cap, *(t.data_ptr() for t in out), n_values,
+                    [(v.data_ptr() if n_values else 0, (m.data_ptr() if m is not None and n_values else 0), dt, ops) for v, m, dt, ops in cols],
+                    [{name: (t.data_ptr() if cap else 0) for name, t in r.items()} for r in results])
             if not fits:
                 raise ValueError(f"merge output buffers hold fewer than {n} intervals")
         finally:
             ix.close()
-        return tuple(t[:n] for t in out)
+        table = tuple(t[:n] for t in out)
+        if agg is None:
+            return table
+        return (*table, [{name: t[:n] for name, t in r.items()} for r in results])
 
     def depth(self, frame: DeviceSide, strict: bool, n_contigs: int, out=None):
         """Blocks of constant coverage >= 1 of one frame -> (contig, start, end, depth) int32 tensors, (contig, start) order.

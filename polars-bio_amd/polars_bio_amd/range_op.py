@@ -827,6 +827,78 @@ def depth_summary(
     return A.from_arrow(t, output_type, zero_based)
 
 
+_AGG_OP_NAMES = ("sum", "min", "max", "mean", "count")
+_MAX_AGG_COLS = 16          # include/ivjoin.h: IVJ_MAX_AGG_COLS
+
+
+def _validate_agg(agg, t: pa.Table, cols, on_cols) -> list:
+    """pb.merge's ``agg`` -> [(column, [operations])] in the order given; ValueError (naming the column) on anything the engine
+    cannot aggregate."""
+    if not isinstance(agg, dict) or not agg:
+        raise ValueError("agg must be a non-empty dict of column -> operation or list of operations, "
+                         'e.g. {"score": ["sum", "max"], "qual": "mean"}')
+    if len(agg) > _MAX_AGG_COLS:
+        raise ValueError(f"agg: at most {_MAX_AGG_COLS} value columns per call, got {len(agg)}")
+    spec, taken = [], set(cols) | set(on_cols or ()) | {"n_intervals"}
+    for name, ops in agg.items():
+        if name not in t.column_names:
+            raise ValueError(f"agg: column '{name}' not found in {t.column_names}")
+        if name in cols or name in (on_cols or ()):
+            raise ValueError(f"agg: column '{name}' is an interval or on_cols column and cannot be aggregated")
+        typ = t.schema.field(name).type
+        if not (pa.types.is_floating(typ) and typ.bit_width in (32, 64)) and not pa.types.is_signed_integer(typ) and not (
+                pa.types.is_unsigned_integer(typ) and typ.bit_width <= 32):
+            raise ValueError(f"agg: column '{name}' has type {typ}; signed integers, unsigned integers up to 32 bits, float32 and "
+                             "float64 can be aggregated")
+        ops = [ops] if isinstance(ops, str) else list(ops) if isinstance(ops, (list, tuple)) else None
+        if not ops:
+            raise ValueError(f"agg: column '{name}' needs an operation or a non-empty list of operations out of {list(_AGG_OP_NAMES)}")
+        for op in ops:
+            if op not in _AGG_OP_NAMES:
+                raise ValueError(f"agg: unknown operation {op!r} for column '{name}': expected one of {list(_AGG_OP_NAMES)}")
+            out = f"{name}_{op}"
+            if out in taken:
+                raise ValueError(f"agg: the output column '{out}' of column '{name}' collides with another output column")
+            taken.add(out)
+        spec.append((name, ops))
+    return spec
+
+
+def _agg_input(t: pa.Table, name: str, keep):
+    """One value column as the engine reads it: (int64 / float64 values with 0 at the nulls, validity or None, ops are the
+    caller's), rows outside ``keep`` dropped."""
+    col = t.column(name)
+    col = col.combine_chunks() if isinstance(col, pa.ChunkedArray) else col
+    wide = pa.float64() if pa.types.is_floating(col.type) else pa.int64()
+    valid = None
+    if col.null_count:
+        valid = pc.is_valid(col).to_numpy(zero_copy_only=False)
+        col = pc.fill_null(col, pa.scalar(0, type=col.type))
+    values = pc.cast(col, wide).to_numpy(zero_copy_only=False)
+    if keep is not None:
+        values, valid = values[keep], (valid[keep] if valid is not None else None)
+    return np.ascontiguousarray(values), valid
+
+
+def _agg_outputs(name: str, ops, typ: pa.DataType, res: dict) -> dict:
+    """The result columns <name>_<op> of one value column: sum Int64 / Float64, min / max the column's own type, mean Float64,
+    count Int64; min / max / mean are null where no valid value was merged."""
+    empty = res["count"] == 0
+    mask = empty if empty.any() else None
+    out = {}
+    for op in ops:
+        a = res[op]
+        if op in ("min", "max"):
+            if mask is not None:
+                a = np.where(mask, 0, a)
+            out[f"{name}_{op}"] = pc.cast(pa.array(a, mask=mask), typ)
+        elif op == "mean":
+            out[f"{name}_{op}"] = pa.array(a, type=pa.float64(), mask=mask)
+        else:
+            out[f"{name}_{op}"] = pa.array(a)
+    return out
+
+
 def merge(
     df,
     min_dist: int = 0,
@@ -834,6 +906,8 @@ def merge(
     on_cols: Union[list, None] = None,
     output_type: str = "polars.LazyFrame",
     projection_pushdown: bool = True,
+    *,
+    agg: Union[dict, None] = None,
 ):
     """Merge overlapping intervals (reference: range_op.py:599-657; MergeProvider, src/operation.rs:352-381).
     Output: (chrom, start: Int64, end: Int64, n_intervals: Int64) in (chrom, start) order
@@ -841,12 +915,21 @@ def merge(
     intervals stay apart (tests/_expected.py:174-181).
 
     ``on_cols``: intervals merge only within groups of equal (chrom, on values); output (chrom, start, end, <on_cols...>,
-    n_intervals) in (chrom, on values, start) order; rows with a null on-value are dropped, as rows with a null chrom are."""
+    n_intervals) in (chrom, on values, start) order; rows with a null on-value are dropped, as rows with a null chrom are.
+
+    ``agg``: value columns summarised per merged interval, as ``bedtools merge -c/-o`` does:
+    ``agg={"score": ["sum", "max"], "qual": "mean"}`` appends ``score_sum``, ``score_max`` and ``qual_mean`` after
+    ``n_intervals``, in the order of the dict and of each list.  Operations: ``sum`` (Int64 for integer columns, wrapping
+    modulo 2^64; Float64 for float columns), ``min`` / ``max`` (the column's own type), ``mean`` (Float64), ``count`` (Int64,
+    the non-null values).  Columns may be signed integers, unsigned integers up to 32 bits, float32 or float64.  Null values
+    are skipped: ``sum`` over no value is 0, ``min`` / ``max`` / ``mean`` over none are null.  Rows that ``merge`` drops take
+    their values with them."""
     on_cols = _validate_overlap_input(cols, cols, on_cols, ("_1", "_2"), output_type)
     _check_on_cols_present(on_cols, df)
     zero_based = validate_coordinate_system_single(df)
     cols = list(DEFAULT_INTERVAL_COLUMNS if cols is None else cols)
     t = A.to_arrow(df)
+    spec = _validate_agg(agg, t, cols, on_cols) if agg is not None else None
     side, n_contigs, dictionary = A.encode_frame(t, cols)
     gchrom = None
     if on_cols:
@@ -856,8 +939,14 @@ def merge(
         _, side, groups, table = A.group_sides(empty, side, n_contigs, [np.empty(0, np.int32)] * len(on_cols), codes, cards, on_cols)
         n_contigs, gchrom = max(groups, 1), table
     keep = side[0] >= 0                                   # rows with a null chrom (or on-value) belong to no contig
-    side = tuple(a[keep] for a in side) if not keep.all() else side
-    c, s, e, n = default_engine().merge(side, strict=zero_based, n_contigs=n_contigs, min_dist=int(min_dist))
+    dropped = not keep.all()
+    side = tuple(a[keep] for a in side) if dropped else side
+    if spec is None:
+        c, s, e, n = default_engine().merge(side, strict=zero_based, n_contigs=n_contigs, min_dist=int(min_dist))
+    else:
+        # count always travels along: it tells where min / max / mean are null
+        inputs = [(*_agg_input(t, name, keep if dropped else None), list(ops) + ["count"]) for name, ops in spec]
+        c, s, e, n, results = default_engine().merge_agg(side, strict=zero_based, n_contigs=n_contigs, agg=inputs, min_dist=int(min_dist))
     c = np.ascontiguousarray(c, np.int32)
     chrom_ids = c if gchrom is None else A.H.take(np.ascontiguousarray(gchrom[:, 0]), c)
     data = {cols[0]: pc.cast(pc.take(dictionary, pa.array(chrom_ids, type=pa.int32())), pa.string()),
@@ -866,6 +955,9 @@ def merge(
         values = pc.take(dicts[j], pa.array(A.H.take(np.ascontiguousarray(gchrom[:, 1 + j]), c), type=pa.int32()))
         data[name] = A.cast_on_values(values, t.schema.field(name).type)
     data["n_intervals"] = pa.array(n, type=pa.int64())
+    if spec is not None:
+        for (name, ops), res in zip(spec, results):
+            data.update(_agg_outputs(name, ops, t.schema.field(name).type, res))
     return A.from_arrow(pa.table(data), output_type, zero_based)
 
 
