@@ -277,6 +277,48 @@ int ivj_overlap_thresh_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_de
 int ivj_count_overlaps_thresh_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, const ivj_opts* opts, const ivj_thresholds* thr_dev,
                                   int64_t* counts_dev);
 
+/* ---- join kinds of pb.overlap other than inner: semi, anti, left outer (bedtools intersect -u / -v / -loj) -------------------------
+ * "The predicate" is the plain overlap predicate of ivj_overlap, or -- with a non-NULL ivj_thresholds -- the thresholded one of the
+ * section above.  With cnt[i] = what ivj_count_overlaps (ivj_count_overlaps_thresh) returns for probe row i under the very same
+ * arguments:
+ *   semi   IVJ_SELECT_SEMI   the probe rows with cnt[i] > 0, each once, in ascending row order
+ *   anti   IVJ_SELECT_ANTI   the probe rows with cnt[i] == 0, in ascending row order
+ *   left   ivj_overlap_outer the inner pairs exactly as the inner join of the same call returns them (ivj_overlap, or
+ *                            ivj_overlap_thresh with thresholds), followed by one pair (i, -1) for every anti row i, ascending
+ * Rows that can match nothing are anti rows and appear in the left outer join with -1: a null chrom or on-value (contig id < 0), a
+ * contig id outside the dictionary (>= n_contigs) and, under thresholds, rows that cover no position or whose own minimum is
+ * "never".  An empty build side makes every probe row an anti row.  The semi and anti outputs are identical from run to run.
+ * The per-probe counts come from the count kernels as they are, stay in a scratch column of the context and are consumed where they
+ * lie by an ordered stream compaction (csrc/select.hip.h): counts and flags never leave the device, no pair is enumerated for semi
+ * or anti.  A non-NULL `thr` with nothing set is IVJ_EINVAL, as for the thresholded entries; an unknown `mode` is IVJ_EINVAL.
+ * (New entries and a new struct change no existing struct or signature: IVJ_ABI_VERSION stays.) */
+#define IVJ_SELECT_SEMI 0
+#define IVJ_SELECT_ANTI 1
+typedef struct {
+    int32_t* rows;     /* selected probe rows, ascending; library-owned (ivj_rowsel_free) */
+    int64_t n;
+} ivj_rowsel;
+
+/* Host path.  The reported row is the row's position in the probe columns (row_id of a host side is not read, as in ivj_overlap). */
+int ivj_overlap_select(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts,
+                       const ivj_thresholds* thr /* NULL = plain predicate */, int32_t mode, ivj_rowsel* out);
+void ivj_rowsel_free(ivj_rowsel* r);
+/* Device path on an index of ivj_index_build_dev (a sweep-only index is IVJ_ESTATE).  The reported id is probe_dev->row_id[position]
+ * when the side has row ids, else the position; the ORDER is that of the positions.  The capacity contract of
+ * ivj_overlap_thresh_dev: *n_rows always receives the total; IVJ_ECAPACITY when it exceeds `capacity`, and nothing is written then.
+ * NULL buffers with capacity 0 = count only (IVJ_OK).  pad_dev (NULL, or `capacity` values) receives -1 at every output position
+ * that rows_dev receives a row at: with rows_dev = probe_idx + n_inner and pad_dev = build_idx + n_inner an anti selection appends
+ * the unmatched rows of a left outer join behind the inner pairs of the caller's two pair columns.  The two pointers need 4-byte
+ * alignment only.  Blocks until the total is known (one 8-byte D2H). */
+int ivj_overlap_select_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, const ivj_opts* opts,
+                           const ivj_thresholds* thr_dev /* NULL = plain predicate */, int32_t mode, int32_t* rows_dev,
+                           int32_t* pad_dev /* NULL, or receives -1 */, int64_t capacity, int64_t* n_rows);
+/* Left outer join on the host path: the inner pairs from the existing drivers (without thresholds the count -> fill pair of
+ * ivj_overlap, with thresholds count -> scan -> emit of ivj_overlap_thresh; their order contracts hold for the inner part), then
+ * (row, -1) per anti row, in one buffer sized for both.  Every probe row occurs at least once.  Free with ivj_pairs_free. */
+int ivj_overlap_outer(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts,
+                      const ivj_thresholds* thr /* NULL = plain predicate */, ivj_pairs* out);
+
 /* ---- row materialisation -------------------- *
  * The step right after the join: gather the columns of both sides for every emitted pair     *
  * (reference: the renaming SELECT of src/operation.rs:272-301 over the joined batches).      *

@@ -133,6 +133,7 @@ struct ivj_ctx {
     struct StreamBufs { int32_t* h_in = nullptr; int32_t* d_in = nullptr; size_t in_cap = 0; char* d_out = nullptr; size_t d_out_cap = 0;
                         char* h_out = nullptr; size_t h_out_cap = 0; } st_cache[3];
     char* lb_buf = nullptr; size_t lb_cap = 0;        // status words + ticket of the single-launch look-back scans (lb_scan_u32)
+    char* sel_buf = nullptr; size_t sel_cap = 0;      // semi / anti / outer join (host_select.hip.h): per-probe counts, tile totals, scan partials
     char* sl_buf = nullptr;
     size_t sl_cap = 0;
     int4* sl_rec = nullptr;

@@ -35,6 +35,7 @@
 #include "setop.hip.h"
 #include "multi.hip.h"
 #include "thresh.hip.h"
+#include "select.hip.h"
 #include "merge_agg.hip.h"
 
 using namespace ivj;
@@ -53,6 +54,7 @@ using namespace ivj;
 #include "host_setop.hip.h"
 #include "host_multi.hip.h"
 #include "host_thresh.hip.h"
+#include "host_select.hip.h"
 #include "host_stream.hip.h"
 #include "host_comm.hip.h"
 #include "host_group.hip.h"
@@ -162,6 +164,7 @@ void ivj_ctx_destroy(ivj_ctx* ctx) {
     if (ctx->sl_buf) (void)hipFree(ctx->sl_buf);
     if (ctx->cs_trace_buf) (void)hipFree(ctx->cs_trace_buf);
     if (ctx->lb_buf) (void)hipFree(ctx->lb_buf);
+    if (ctx->sel_buf) (void)hipFree(ctx->sel_buf);
     for (auto& cb : ctx->st_cache) free_stream_bufs(cb);
     if (ctx->ix_cache) (void)hipFree(ctx->ix_cache);
     if (ctx->nl_cache) (void)hipFree(ctx->nl_cache);
@@ -1343,6 +1346,106 @@ int ivj_count_overlaps_thresh(ivj_ctx* ctx, const ivj_side* probe, const ivj_sid
     HostXfer copy(ctx->stream, &ctx->xfer);
     copy.d2h(counts, dc.p, (size_t)probe->n * 8);
     HIP_TRY(copy.finish());
+    return IVJ_OK;
+} IVJ_ABI_CATCH
+
+// ---------------------------------------------------------------- join kinds: semi, anti, left outer (select.hip.h, host_select.hip.h)
+
+int ivj_overlap_select_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, const ivj_opts* opts, const ivj_thresholds* thr_dev,
+                           int32_t mode, int32_t* rows_dev, int32_t* pad_dev, int64_t capacity, int64_t* n_rows) try {
+    if (!ctx || !ix || !n_rows) return fail(IVJ_EINVAL, "ctx, index or n_rows is NULL");
+    *n_rows = 0;
+    IVJ_TRY(check_opts(opts));
+    IVJ_TRY(check_side(probe_dev, "probe"));
+    if (thr_dev) IVJ_TRY(check_thresholds(thr_dev));
+    IVJ_TRY(check_select_mode(mode));
+    if (capacity < 0 || (capacity > 0 && !rows_dev)) return fail(IVJ_EINVAL, "bad output buffers");
+    DeviceGuard g(ctx->device);
+    return overlap_select_dev(ctx, ix, probe_dev, opts, thr_dev, mode, rows_dev, pad_dev, capacity, n_rows);
+} IVJ_ABI_CATCH
+
+void ivj_rowsel_free(ivj_rowsel* r) {
+    if (!r) return;
+    std::free(r->rows);
+    r->rows = nullptr; r->n = 0;
+}
+
+int ivj_overlap_select(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, const ivj_thresholds* thr,
+                       int32_t mode, ivj_rowsel* out) try {
+    if (!ctx || !out) return fail(IVJ_EINVAL, "ctx or out is NULL");
+    out->rows = nullptr; out->n = 0;
+    IVJ_TRY(check_opts(opts));
+    IVJ_TRY(check_side(probe, "probe"));
+    IVJ_TRY(check_side(build, "build"));
+    if (thr) IVJ_TRY(check_thresholds(thr));
+    IVJ_TRY(check_select_mode(mode));
+    if (probe->n == 0) return IVJ_OK;
+    DeviceGuard g(ctx->device);
+    SelectHost U;
+    IVJ_TRY(select_upload(ctx, probe, build, opts, thr, U));
+    SelectPlan S;
+    int64_t total = 0;
+    IVJ_TRY(select_count(ctx, U.H.h.ix, &U.H.dp.s, opts, U.dthr, mode, S, &total));
+    if (total == 0) return IVJ_OK;
+    DevBuf rows;
+    hipError_t e = hipMalloc(&rows.p, (size_t)total * 4);
+    if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(rows): ") + hipGetErrorString(e));
+    IVJ_TRY(select_emit(ctx, S, (int32_t*)rows.p, nullptr));
+    out->rows = (int32_t*)host_result_alloc((size_t)total * 4);
+    if (!out->rows) return fail(IVJ_ENOMEM, "host malloc(rows)");
+    HostXfer copy(ctx->stream, &ctx->xfer);
+    copy.d2h(out->rows, rows.p, (size_t)total * 4);
+    const hipError_t ce = copy.finish();
+    if (ce != hipSuccess) { ivj_rowsel_free(out); return fail(IVJ_EHIP, std::string("D2H(rows): ") + hipGetErrorString(ce)); }
+    out->n = total;
+    return IVJ_OK;
+} IVJ_ABI_CATCH
+
+int ivj_overlap_outer(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, const ivj_thresholds* thr,
+                      ivj_pairs* out) try {
+    if (!ctx || !out) return fail(IVJ_EINVAL, "ctx or out is NULL");
+    out->n_pairs = 0; out->probe_idx = nullptr; out->build_idx = nullptr;
+    IVJ_TRY(check_opts(opts));
+    IVJ_TRY(check_side(probe, "probe"));
+    IVJ_TRY(check_side(build, "build"));
+    if (thr) IVJ_TRY(check_thresholds(thr));
+    if (probe->n == 0) return IVJ_OK;
+    DeviceGuard g(ctx->device);
+    SelectHost U;
+    IVJ_TRY(select_upload(ctx, probe, build, opts, thr, U));
+    ivj_index* ix = U.H.h.ix;
+    const ivj_side* dp = &U.H.dp.s;
+    // the anti rows first: their counts and tile bases stay in the selection scratch while the inner join runs
+    SelectPlan S;
+    ThreshPlan plan;
+    int64_t n_anti = 0, n_inner = 0;
+    if (thr) IVJ_TRY(select_count(ctx, ix, dp, opts, U.dthr, IVJ_SELECT_ANTI, S, &n_anti, &plan, &n_inner));
+    else {
+        IVJ_TRY(select_count(ctx, ix, dp, opts, nullptr, IVJ_SELECT_ANTI, S, &n_anti));
+        IVJ_TRY(overlap_count(ctx, ix, dp, opts, &n_inner));
+    }
+    const int64_t total = n_inner + n_anti;
+    if (total == 0) return IVJ_OK;
+    if (!host_result_fits((size_t)total * 8))
+        return fail(IVJ_ENOMEM, "the result (" + std::to_string(total) + " pairs, " + std::to_string((size_t)total * 8 >> 20) + " MiB) does not fit the available host memory");
+    DevBuf op, ob;
+    hipError_t e = hipMalloc(&op.p, (size_t)total * 4);
+    if (e == hipSuccess) e = hipMalloc(&ob.p, (size_t)total * 4);
+    if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(pairs): ") + hipGetErrorString(e));
+    if (n_inner > 0) {
+        if (thr) IVJ_TRY(thresh_emit(ctx, ix, plan, (int32_t*)op.p, (int32_t*)ob.p));
+        else IVJ_TRY(overlap_fill(ctx, ix, dp, opts, (int32_t*)op.p, (int32_t*)ob.p, n_inner));
+    }
+    if (n_anti > 0) IVJ_TRY(select_emit(ctx, S, (int32_t*)op.p + n_inner, (int32_t*)ob.p + n_inner));
+    out->probe_idx = (int32_t*)host_result_alloc((size_t)total * 4);
+    out->build_idx = (int32_t*)host_result_alloc((size_t)total * 4);
+    if (!out->probe_idx || !out->build_idx) { ivj_pairs_free(out); return fail(IVJ_ENOMEM, "host malloc(pairs)"); }
+    HostXfer copy(ctx->stream, &ctx->xfer);
+    copy.d2h(out->probe_idx, op.p, (size_t)total * 4);
+    copy.d2h(out->build_idx, ob.p, (size_t)total * 4);
+    const hipError_t ce = copy.finish();
+    if (ce != hipSuccess) { ivj_pairs_free(out); return fail(IVJ_EHIP, std::string("D2H(pairs): ") + hipGetErrorString(ce)); }
+    out->n_pairs = total;
     return IVJ_OK;
 } IVJ_ABI_CATCH
 

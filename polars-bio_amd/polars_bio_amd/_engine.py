@@ -30,6 +30,7 @@ ABI_SYMBOLS = [
     "ivj_index_build_dev", "ivj_index_free", "ivj_overlap_count_dev", "ivj_overlap_fill_dev", "ivj_overlap_fused_dev",
     "ivj_count_overlaps_dev", "ivj_nearest_dev",
     "ivj_overlap_thresh", "ivj_count_overlaps_thresh", "ivj_overlap_thresh_dev", "ivj_count_overlaps_thresh_dev",
+    "ivj_overlap_select", "ivj_rowsel_free", "ivj_overlap_select_dev", "ivj_overlap_outer",
     "ivj_side_from_arrow", "ivj_materialize_dev", "ivj_overlap_fused_rows_dev", "ivj_take_dev", "ivj_take", "ivj_overlap_rows", "ivj_rows_free", "ivj_rows_export_arrow",
     "ivj_subtract", "ivj_complement", "ivj_pieces_free", "ivj_subtract_dev",
     "ivj_merge", "ivj_merged_free", "ivj_cluster", "ivj_coverage", "ivj_cluster_dev", "ivj_merge_dev", "ivj_coverage_dev",
@@ -75,6 +76,10 @@ ROW_COLUMNS = ("probe_idx", "build_idx", "contig", "start_1", "end_1", "start_2"
 
 IVJ_ECAPACITY, IVJ_ESTATE, IVJ_EPEER = -4, -5, -6
 
+# ivj_overlap_select / ivj_overlap_select_dev (include/ivjoin.h: IVJ_SELECT_*)
+SELECT_SEMI, SELECT_ANTI = 0, 1
+SELECT_MODES = {"semi": SELECT_SEMI, "anti": SELECT_ANTI}
+
 # ivj_thresholds minima (include/ivjoin.h): uint32 base counts, 0 = no requirement, THRESH_NEVER = the row never matches
 THRESH_NEVER = 0xFFFFFFFF
 
@@ -113,6 +118,10 @@ class _Opts(C.Structure):
 
 class _Thresholds(C.Structure):
     _fields_ = [("min_overlap", C.c_uint32), ("probe_min", C.c_void_p), ("build_min", C.c_void_p)]
+
+
+class _RowSel(C.Structure):
+    _fields_ = [("rows", C.POINTER(C.c_int32)), ("n", C.c_int64)]
 
 
 class _Pairs(C.Structure):
@@ -227,6 +236,11 @@ def load_library() -> C.CDLL:
         L.ivj_count_overlaps_thresh.argtypes = [vp, P, P, O, T, vp]
         L.ivj_overlap_thresh_dev.argtypes = [vp, vp, P, O, T, vp, vp, C.c_int64, C.POINTER(C.c_int64)]
         L.ivj_count_overlaps_thresh_dev.argtypes = [vp, vp, P, O, T, vp]
+        L.ivj_overlap_select.argtypes = [vp, P, P, O, T, C.c_int32, C.POINTER(_RowSel)]
+        L.ivj_rowsel_free.argtypes = [C.POINTER(_RowSel)]
+        L.ivj_rowsel_free.restype = None
+        L.ivj_overlap_select_dev.argtypes = [vp, vp, P, O, T, C.c_int32, vp, vp, C.c_int64, C.POINTER(C.c_int64)]
+        L.ivj_overlap_outer.argtypes = [vp, P, P, O, T, C.POINTER(_Pairs)]
         L.ivj_materialize_dev.argtypes = [vp, P, P, C.POINTER(_Rows)]
         L.ivj_overlap_fused_rows_dev.argtypes = [vp, vp, P, O, C.POINTER(_Rows), C.POINTER(C.c_int64)]
         L.ivj_take_dev.argtypes = [vp, vp, C.c_int32, vp, C.c_int64, vp, vp]
@@ -414,6 +428,17 @@ def make_thresholds(min_overlap: int = 0, probe_min_ptr: int = 0, build_min_ptr:
     if not 0 <= int(min_overlap) <= THRESH_NEVER:
         raise ValueError(f"min_overlap must fit uint32, got {min_overlap}")
     return _Thresholds(int(min_overlap), probe_min_ptr or None, build_min_ptr or None)
+
+
+def select_mode(mode) -> int:
+    """"semi" / "anti" or SELECT_SEMI / SELECT_ANTI -> the IVJ_SELECT_* code (ValueError otherwise)."""
+    if isinstance(mode, str):
+        if mode not in SELECT_MODES:
+            raise ValueError(f"unknown selection mode '{mode}': one of {sorted(SELECT_MODES)}")
+        return SELECT_MODES[mode]
+    if isinstance(mode, (bool, np.bool_)) or int(mode) not in SELECT_MODES.values():
+        raise ValueError(f"unknown selection mode {mode!r}")
+    return int(mode)
 
 
 def _setop_code(op) -> int:
@@ -949,6 +974,49 @@ class Engine:
         del keep_p, keep_b, keep_t
         return counts
 
+    def _optional_thresholds(self, ps, bs, min_overlap, probe_min, build_min):
+        """-> (pointer to an ivj_thresholds or None for the plain predicate, keep-alive)."""
+        if not min_overlap and probe_min is None and build_min is None:
+            return None, None
+        t, keep = self._host_thresholds(ps, bs, min_overlap, probe_min, build_min)
+        return C.byref(t), (t, keep)
+
+    def overlap_select(self, probe, build, strict: bool, n_contigs: int, mode, min_overlap: int = 0, probe_min=None, build_min=None,
+                       partition_mode: int = 0) -> np.ndarray:
+        """Semi / anti join (ivj_overlap_select): the probe rows with at least one (mode "semi" / SELECT_SEMI) or no (mode "anti" /
+        SELECT_ANTI) build row under the predicate -- the plain one, or the thresholded one when min_overlap / probe_min / build_min
+        are given -- as an ascending int32 array.  The counts stay on the device; no pair is enumerated."""
+        mode = select_mode(mode)
+        ps, keep_p = _host_side(*probe)
+        bs, keep_b = _host_side(*build)
+        t, keep_t = self._optional_thresholds(ps, bs, min_overlap, probe_min, build_min)
+        o = make_opts(strict, n_contigs, partition_mode=partition_mode)
+        out = _RowSel()
+        _check(self.L, self.L.ivj_overlap_select(self.h, C.byref(ps), C.byref(bs), C.byref(o), t, mode, C.byref(out)), "ivj_overlap_select")
+        del keep_p, keep_b, keep_t
+        try:
+            return np.ctypeslib.as_array(out.rows, shape=(out.n,)).copy() if out.n else np.empty(0, np.int32)
+        finally:
+            self.L.ivj_rowsel_free(C.byref(out))
+
+    def overlap_outer(self, probe, build, strict: bool, n_contigs: int, min_overlap: int = 0, probe_min=None, build_min=None,
+                      partition_mode: int = 0):
+        """Left outer join (ivj_overlap_outer): the inner pairs as ``overlap`` (``overlap_thresh`` with thresholds) returns them,
+        then (row, -1) for every probe row without a match, ascending -> (probe_idx, build_idx)."""
+        ps, keep_p = _host_side(*probe)
+        bs, keep_b = _host_side(*build)
+        t, keep_t = self._optional_thresholds(ps, bs, min_overlap, probe_min, build_min)
+        o = make_opts(strict, n_contigs, partition_mode=partition_mode)
+        out = _Pairs()
+        _check(self.L, self.L.ivj_overlap_outer(self.h, C.byref(ps), C.byref(bs), C.byref(o), t, C.byref(out)), "ivj_overlap_outer")
+        del keep_p, keep_b, keep_t
+        n = out.n_pairs
+        if n == 0:
+            self.L.ivj_pairs_free(C.byref(out))
+            return np.empty(0, np.int32), np.empty(0, np.int32)
+        owner = _PairsOwner(load_library(), out)
+        return _owned_view(out.probe_idx, n, owner), _owned_view(out.build_idx, n, owner)
+
     def nearest(self, probe, build, strict: bool, n_contigs: int, k: int = 1, include_overlaps: bool = True,
                 table_mode: int = 0, partition_mode: int = 0, nearest_ignore: int = 0):
         """partition_mode 0 auto / 1 bucket the probe side first / 2 never: same result, probe order kept.
@@ -1041,6 +1109,19 @@ class Engine:
     def count_overlaps_thresh_dev(self, ix: DeviceIndex, probe: _Side, opts: _Opts, thr: _Thresholds, counts_ptr: int):
         _check(self.L, self.L.ivj_count_overlaps_thresh_dev(self.h, ix.handle, C.byref(probe), C.byref(opts), C.byref(thr),
                                                             C.c_void_p(counts_ptr)), "ivj_count_overlaps_thresh_dev")
+
+    def overlap_select_dev(self, ix: DeviceIndex, probe: _Side, opts: _Opts, thr: Optional[_Thresholds], mode: int, rows_ptr: int,
+                           pad_ptr: int, capacity: int):
+        """Semi / anti selection on an index (ivj_overlap_select_dev; thr from make_thresholds with device addresses, or None for the
+        plain predicate) -> (n_rows, fits).  fits=False: nothing was written, grow the buffers to n_rows.  Null buffers with capacity
+        0 count only.  pad_ptr (0 = none) receives -1 wherever rows_ptr receives a row."""
+        n = C.c_int64(0)
+        rc = self.L.ivj_overlap_select_dev(self.h, ix.handle, C.byref(probe), C.byref(opts), C.byref(thr) if thr is not None else None,
+                                           int(mode), C.c_void_p(rows_ptr or None), C.c_void_p(pad_ptr or None), capacity, C.byref(n))
+        if rc == IVJ_ECAPACITY:
+            return n.value, False
+        _check(self.L, rc, "ivj_overlap_select_dev")
+        return n.value, True
 
     def materialize_dev(self, probe: _Side, build: _Side, n_pairs: int, probe_idx_ptr: int, build_idx_ptr: int,
                         contig_ptr: int = 0, start_1_ptr: int = 0, end_1_ptr: int = 0, start_2_ptr: int = 0, end_2_ptr: int = 0):

@@ -16,7 +16,7 @@ import torch  # noqa: F401  (must precede the dlopen of libivjoin_hip.so in this
 from typing import Optional, Tuple
 
 from ._engine import (AGG_F64, AGG_I64, AGG_OPS, MULTI_CONSENSUS, MULTI_SEGMENTS, DeviceIndex, Engine, agg_ops_mask, check_multi, make_opts,
-                      make_thresholds)
+                      make_thresholds, select_mode)
 
 
 class DeviceSide:
@@ -229,6 +229,40 @@ class DeviceJoin:
             if own:
                 ix.close()
         return out
+
+    # ---- join kinds: semi / anti (include/ivjoin.h: ivj_overlap_select_dev) -------------------------------
+    def overlap_select(self, probe: DeviceSide, build: DeviceSide, strict: bool, n_contigs: int, mode, min_overlap: int = 0, probe_min=None,
+                       build_min=None, index=None, out=None, partition_mode: int = 0):
+        """Semi ("semi") / anti ("anti") join on tensors in HBM: the probe rows (``probe.row_id`` where given, else positions) with
+        at least one / no build row under the predicate -- plain, or thresholded when min_overlap / probe_min / build_min are given
+        (as in ``count_overlaps_thresh``) -> int32 tensor, ascending position order.  ``out``: optional preallocated int32 CUDA
+        tensor, used when it holds the result (the filled slice comes back)."""
+        torch = self.torch
+        mode = select_mode(mode)
+        opts = make_opts(strict, n_contigs, partition_mode=partition_mode)
+        plain = not min_overlap and probe_min is None and build_min is None
+        thr = None if plain else self._thresholds(probe, build, min_overlap, probe_min, build_min)
+        if build.n == 0:
+            plain, thr = True, None                            # every count is 0 under either predicate
+        if probe.n == 0:
+            return torch.empty(0, dtype=torch.int32, device=probe.start.device)
+        own = index is None
+        ix = self.engine.index_build_dev(build.as_c(), opts, plain) if own else index
+        try:
+            side = probe.as_c()
+            if out is not None:
+                total, fits = self.engine.overlap_select_dev(ix, side, opts, thr, mode, out.data_ptr(), 0, out.numel())
+                if fits:
+                    return out[:total]
+            else:
+                total, _ = self.engine.overlap_select_dev(ix, side, opts, thr, mode, 0, 0, 0)
+            rows = torch.empty(total, dtype=torch.int32, device=probe.start.device)
+            if total:
+                self.engine.overlap_select_dev(ix, side, opts, thr, mode, rows.data_ptr(), 0, total)
+        finally:
+            if own:
+                ix.close()
+        return rows
 
     # ---- sort-scan family (SURVEY.md section 8f row 2) ---------------------------------------------
     def coverage(self, probe: DeviceSide, build: DeviceSide, strict: bool, n_contigs: int, index=None, out=None):

@@ -514,6 +514,7 @@ def overlap(
     min_overlap: Union[int, None] = None,
     min_frac1: Union[float, None] = None,
     min_frac2: Union[float, None] = None,
+    how: Literal["inner", "left", "semi", "anti"] = "inner",
 ):
     """Find pairs of overlapping genomic intervals (reference: range_op.py:117-256).
 
@@ -543,7 +544,22 @@ def overlap(
     behave as without thresholds.  A thresholded call is EAGER whatever the ``output_type``: the finished table is converted,
     ``limit`` takes its head, and ``pyarrow.RecordBatchReader`` is a reader over it; ``low_memory`` is not applied.  The streaming
     entries (``overlap_batches``) and a multi-device default engine take no thresholds (the latter raises NotImplementedError).
-    Invalid thresholds raise ValueError."""
+    Invalid thresholds raise ValueError.
+
+    Join kinds (keyword-only ``how``; bedtools ``intersect -u / -v / -loj``).  ``"inner"`` (default) is everything above.
+    ``"semi"``: the df1 rows that overlap at least one df2 row, each once (``-u``); ``"anti"``: the df1 rows that overlap none
+    (``-v``) -- both return df1's columns as they are (no suffix), in df1 order.  ``"left"``: the joined columns of the inner
+    join, followed by one row per unmatched df1 row whose df2 columns are all null (``-loj``).  "Overlap" is the predicate of the
+    call: with ``min_overlap`` / ``min_frac1`` / ``min_frac2`` the thresholded one.  Rows that can match nothing (null chrom or
+    on-value, and under thresholds rows that cover no position) are unmatched rows; an empty df2 leaves every df1 row unmatched.
+    The selection runs on the device over the per-row counts of ``count_overlaps``; no pair is enumerated for semi / anti.  A
+    non-inner ``how`` composes with ``on_cols``, ``cols1`` / ``cols2``, ``suffixes`` and the thresholds; it is EAGER whatever the
+    ``output_type`` (``limit`` takes the head), ``low_memory`` is not applied, ``overlap_output`` must be "join" and
+    ``distinct_output`` False (ValueError otherwise, as for an unknown ``how``); a multi-device default engine raises
+    NotImplementedError.  ``overlap_batches`` takes no ``how``."""
+    how = _validate_how(how, overlap_output, distinct_output)
+    if how != "inner":
+        return _overlap_join_kind(how, df1, df2, suffixes, on_cols, cols1, cols2, output_type, limit, min_overlap, min_frac1, min_frac2)
     if min_overlap is not None or min_frac1 is not None or min_frac2 is not None:
         return _overlap_thresholded(df1, df2, suffixes, on_cols, cols1, cols2, overlap_output, distinct_output, output_type, limit,
                                     min_overlap, min_frac1, min_frac2)
@@ -595,6 +611,48 @@ def _overlap_thresholded(df1, df2, suffixes, on_cols, cols1, cols2, overlap_outp
     pm, bm = _threshold_minima(probe, build, zero_based, f1, f2)
     p_idx, b_idx = eng.overlap_thresh(probe, build, strict=zero_based, n_contigs=n_contigs, min_overlap=mo, probe_min=pm, build_min=bm)
     return _finish_eager(_assemble_overlap(t1, t2, p_idx, b_idx, mode, distinct_output, suffixes, keys), output_type, zero_based, limit)
+
+
+JOIN_KINDS = ("inner", "left", "semi", "anti")
+
+
+def _validate_how(how, overlap_output, distinct_output) -> str:
+    """ValueError: an unknown ``how``; a non-inner ``how`` together with ``overlap_output != "join"`` or ``distinct_output``."""
+    if not isinstance(how, str) or how not in JOIN_KINDS:
+        raise ValueError(f"how must be one of {list(JOIN_KINDS)}, got {how!r}")
+    if how != "inner":
+        if _parse_overlap_output_mode(overlap_output) != OverlapOutputMode.Join:
+            raise ValueError(f"how='{how}' takes overlap_output='join' only: semi / anti already return df1's columns")
+        if distinct_output:
+            raise ValueError(f"how='{how}' does not take distinct_output: semi / anti report every df1 row once")
+    return how
+
+
+def _join_kind_engine():
+    eng = default_engine()
+    if not hasattr(eng, "overlap_select") or not hasattr(eng, "overlap_outer"):
+        raise NotImplementedError(f"how='left' / 'semi' / 'anti' need a single-device engine; the default engine is a "
+                                  f"{type(eng).__name__} (several devices), which has no semi, anti or outer join")
+    return eng
+
+
+def _overlap_join_kind(how, df1, df2, suffixes, on_cols, cols1, cols2, output_type, limit, min_overlap, min_frac1, min_frac2):
+    mo, f1, f2 = _validate_overlap_thresholds(min_overlap, min_frac1, min_frac2)
+    on_cols = _validate_overlap_input(cols1, cols2, on_cols, suffixes, output_type)
+    _check_on_cols_present(on_cols, df1, df2)
+    zero_based = validate_coordinate_systems(df1, df2)
+    eng = _join_kind_engine()
+    t1, t2, probe, build, n_contigs, keys = _prepare(df1, df2, cols1, cols2, on_cols)
+    pm, bm = _threshold_minima(probe, build, zero_based, f1, f2)
+    kw = dict(strict=zero_based, n_contigs=n_contigs, min_overlap=mo, probe_min=pm, build_min=bm)
+    k1, k2 = (keys[0], keys[1], keys[4]), (keys[2], keys[3], keys[4])
+    if how == "left":
+        p_idx, b_idx = eng.overlap_outer(probe, build, **kw)
+        left, right = A.take_rows(t1, p_idx, chrom=k1), A.take_rows(t2, b_idx, nullable=True, chrom=k2)
+        table = A.hconcat(A.with_suffix(left, suffixes[0]), A.with_suffix(right, suffixes[1]))
+    else:
+        table = A.take_rows(t1, eng.overlap_select(probe, build, mode=how, **kw), chrom=k1)
+    return _finish_eager(table, output_type, zero_based, limit)
 
 
 def nearest(
