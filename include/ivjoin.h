@@ -493,6 +493,40 @@ int ivj_merge_agg_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_opts* opts, int64_t
                       int32_t* start_dev, int32_t* end_dev, int64_t* n_intervals_dev, int64_t n_values, int32_t n_cols,
                       const ivj_agg_in* cols, const ivj_agg_out* agg_out, int64_t* n_merged);
 
+/* ---- map_overlaps: build-side value columns reduced over each probe row's overlaps (bedtools map -c / -o) --------------------------
+ * For every probe (df1) row a, over the build (df2) rows b that match a, and per value column of the BUILD side over the VALID
+ * values only: count / sum / min / max / mean exactly as ivj_merge_agg defines them per cluster (count int64; an integer sum
+ * accumulated as uint64, i.e. a wrapping int64; doubles with fmin / fmax, a NaN value makes sum and mean NaN;
+ * mean = (double)sum / (double)count).  sum is 0 and count is 0 where nothing valid matches; min / max / mean are unspecified
+ * there (the front door makes them nulls).
+ * "Matches" with thr == NULL is the plain join's predicate for opts->filter_op, bit for bit: the count of a column without nulls
+ * equals ivj_count_overlaps of the same call, rows that cover no position included.  With an ivj_thresholds it is the thresholded
+ * predicate ov >= max(1, min_overlap, probe_min[a], build_min[b]), "never" honoured: the count then equals
+ * ivj_count_overlaps_thresh.  A non-NULL thr with nothing set is IVJ_EINVAL.
+ * Values are indexed by the row the index reports for a build position (host form: the row's position in the build columns); a
+ * row outside [0, n_values) contributes nothing, as in ivj_merge_agg_dev.  Results are written at the probe's position in the
+ * caller's columns -- one entry per probe row, in probe order, also where the probes are bucketed internally (partition_mode); a
+ * probe row_id is ignored.  A probe row outside the dictionary (null chrom or on-value) gets count 0.  There is no capacity
+ * protocol: every output column holds probe->n entries.  Operations not asked for are not written.
+ * No pair is enumerated and there is no atomic, floating-point or other: integer results are bit-identical from run to run.  A
+ * double sum is evaluated in an order fixed by the sorted order of the index and the kernel's geometry (csrc/overlap_agg.hip.h),
+ * and both index builds keep rows of equal (contig, start) in input order, so double sums repeat bit for bit too, for the same
+ * input rows in the same order on the same library build.  Which of -0.0 / +0.0 a double min / max returns when both occur is
+ * unspecified.  The cost is one sweep over the CANDIDATES (not the matches) per value column.
+ * IVJ_EINVAL as for ivj_merge_agg: n_cols outside [1, IVJ_MAX_AGG_COLS], ops == 0 or with unknown bits, an unknown dtype, NULL
+ * values with build rows present, a NULL output column of an operation that was asked for (with probe rows present).
+ * IVJ_ESTATE: an index without lookup tables (with_end_order & 2).
+ * (New entries change no existing struct or signature: IVJ_ABI_VERSION stays.) */
+/* Host form: agg_out[k].* are CALLER-owned host columns of probe->n entries (NULL where not asked for). */
+int ivj_overlap_agg(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts,
+                    const ivj_thresholds* thr /* NULL = plain predicate */, int32_t n_cols, const ivj_agg_in* cols /* over build rows */,
+                    const ivj_agg_out* agg_out);
+/* Device form on an index of ivj_index_build_dev: values / valid / outputs are device pointers, n_values = rows behind
+ * cols[k].values; enqueued on the context's stream. */
+int ivj_overlap_agg_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, const ivj_opts* opts,
+                        const ivj_thresholds* thr_dev /* NULL = plain predicate */, int64_t n_values, int32_t n_cols,
+                        const ivj_agg_in* cols, const ivj_agg_out* agg_out);
+
 /* ---- depth: run-length coverage blocks of one frame ------------------------------------------------------------------------------
  * The disjoint maximal runs of positions covered by the same number (>= 1) of the frame's rows, in (contig id, start) order: the
  * block form (chrom, start, end, coverage) of the reference's pb.depth (polars_bio/pileup_op.py:94-100), computed from an interval

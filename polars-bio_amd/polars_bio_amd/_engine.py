@@ -35,6 +35,7 @@ ABI_SYMBOLS = [
     "ivj_subtract", "ivj_complement", "ivj_pieces_free", "ivj_subtract_dev",
     "ivj_merge", "ivj_merged_free", "ivj_cluster", "ivj_coverage", "ivj_cluster_dev", "ivj_merge_dev", "ivj_coverage_dev",
     "ivj_merge_agg", "ivj_merge_agg_free", "ivj_merge_agg_dev",
+    "ivj_overlap_agg", "ivj_overlap_agg_dev",
     "ivj_overlap_bases", "ivj_overlap_bases_dev",
     "ivj_depth", "ivj_blocks_free", "ivj_depth_dev", "ivj_depth_summary", "ivj_depth_summary_dev",
     "ivj_setop", "ivj_regions_free", "ivj_set_stats", "ivj_setop_dev", "ivj_set_stats_dev",
@@ -267,6 +268,8 @@ def load_library() -> C.CDLL:
         L.ivj_merge_agg_free.restype = None
         L.ivj_merge_agg_dev.argtypes = [vp, vp, O, C.c_int64, C.c_int64, vp, vp, vp, vp, C.c_int64, C.c_int32, C.POINTER(_AggIn),
                                         C.POINTER(_AggOut), C.POINTER(C.c_int64)]
+        L.ivj_overlap_agg.argtypes = [vp, P, P, O, T, C.c_int32, C.POINTER(_AggIn), C.POINTER(_AggOut)]
+        L.ivj_overlap_agg_dev.argtypes = [vp, vp, P, O, T, C.c_int64, C.c_int32, C.POINTER(_AggIn), C.POINTER(_AggOut)]
         L.ivj_depth.argtypes = [vp, P, O, C.POINTER(_Blocks)]
         L.ivj_blocks_free.argtypes = [C.POINTER(_Blocks)]
         L.ivj_blocks_free.restype = None
@@ -981,6 +984,34 @@ class Engine:
         t, keep = self._host_thresholds(ps, bs, min_overlap, probe_min, build_min)
         return C.byref(t), (t, keep)
 
+    def overlap_agg(self, probe, build, strict: bool, n_contigs: int, agg, min_overlap: int = 0, probe_min=None, build_min=None,
+                    partition_mode: int = 0):
+        """pb.map_overlaps (ivj_overlap_agg): ``agg`` = a list of (values, valid, ops) per value column of the BUILD side, as in
+        ``merge_agg``.  Every probe row reduces the valid values of the build rows it matches -- under the plain predicate, or the
+        thresholded one when min_overlap / probe_min / build_min are given -> [dict per column] mapping each requested name to an
+        array of one entry per probe row, probe order kept: sum int64 (wrapped) / float64, min / max the column's type, mean
+        float64, count int64.  sum and count are 0 where nothing valid matches; min / max / mean are unspecified there."""
+        ps, keep_p = _host_side(*probe)
+        bs, keep_b = _host_side(*build)
+        t, keep_t = self._optional_thresholds(ps, bs, min_overlap, probe_min, build_min)
+        o = make_opts(strict, n_contigs, partition_mode=partition_mode)
+        agg = list(agg)
+        cols = (_AggIn * max(len(agg), 1))()
+        outs = (_AggOut * max(len(agg), 1))()
+        keep, results = [], []
+        for k, (values, valid, ops) in enumerate(agg):
+            values, valid, ops = _agg_column(values, valid, ops, bs.n)
+            keep.append((values, valid))
+            cols[k] = _AggIn(values.ctypes.data if bs.n else None, valid.ctypes.data if valid is not None and bs.n else None,
+                             AGG_I64 if values.dtype == np.int64 else AGG_F64, ops)
+            kinds = {"sum": values.dtype, "min": values.dtype, "max": values.dtype, "mean": np.float64, "count": np.int64}
+            res = {name: np.zeros(ps.n, kinds[name]) for name, bit in AGG_OPS.items() if ops & bit}
+            outs[k] = _AggOut(*(res[name].ctypes.data if name in res and ps.n else None for name in ("sum", "min", "max", "mean", "count")))
+            results.append(res)
+        _check(self.L, self.L.ivj_overlap_agg(self.h, C.byref(ps), C.byref(bs), C.byref(o), t, len(agg), cols, outs), "ivj_overlap_agg")
+        del keep_p, keep_b, keep_t, keep
+        return results
+
     def overlap_select(self, probe, build, strict: bool, n_contigs: int, mode, min_overlap: int = 0, probe_min=None, build_min=None,
                        partition_mode: int = 0) -> np.ndarray:
         """Semi / anti join (ivj_overlap_select): the probe rows with at least one (mode "semi" / SELECT_SEMI) or no (mode "anti" /
@@ -1204,6 +1235,18 @@ class Engine:
             return n.value, False
         _check(self.L, rc, "ivj_merge_agg_dev")
         return n.value, True
+
+    def overlap_agg_dev(self, ix: DeviceIndex, probe: _Side, opts: _Opts, thr: Optional[_Thresholds], n_values: int, cols, outs):
+        """ivj_overlap_agg_dev; ``thr`` None = the plain predicate.  ``cols`` / ``outs`` as in ``merge_agg_dev``, the value columns
+        being the build side's and every output column holding probe.n entries."""
+        k = len(cols)
+        cin = (_AggIn * max(k, 1))()
+        cout = (_AggOut * max(k, 1))()
+        for i, (values_ptr, valid_ptr, dtype, ops) in enumerate(cols):
+            cin[i] = _AggIn(values_ptr or None, valid_ptr or None, int(dtype), int(ops))
+            cout[i] = _AggOut(*(outs[i].get(name) or None for name in ("sum", "min", "max", "mean", "count")))
+        _check(self.L, self.L.ivj_overlap_agg_dev(self.h, ix.handle, C.byref(probe), C.byref(opts), C.byref(thr) if thr is not None else None,
+                                                  int(n_values), k, cin, cout), "ivj_overlap_agg_dev")
 
     def depth_dev(self, ix: DeviceIndex, opts: _Opts, capacity: int, contig_ptr: int, start_ptr: int, end_ptr: int, depth_ptr: int):
         """-> (n_blocks, fits).  fits=False: nothing was written, grow the buffers to n_blocks."""

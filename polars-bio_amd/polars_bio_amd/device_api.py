@@ -230,6 +230,49 @@ class DeviceJoin:
                 ix.close()
         return out
 
+    # ---- map_overlaps (include/ivjoin.h: ivj_overlap_agg_dev) ------------------------------------------
+    def overlap_agg(self, probe: DeviceSide, build: DeviceSide, strict: bool, n_contigs: int, agg, min_overlap: int = 0, probe_min=None,
+                    build_min=None, index=None, partition_mode: int = 0):
+        """Build-side value columns reduced over each probe row's matches (ivj_overlap_agg_dev), all in HBM.  ``agg``: a list of
+        (values, valid, ops) per value column as in ``merge`` -- the values indexed by the build side's rows (by its ``row_id``
+        where it carries one; rows beyond the column's length contribute nothing).  The predicate is the plain one, or the
+        thresholded one when min_overlap / probe_min / build_min are given (as in ``count_overlaps_thresh``).  -> one dict per
+        column, name -> tensor of probe.n elements in probe order: sum int64 (wrapped) / float64, min / max the column's type,
+        mean float64, count int64.  sum and count are 0 where nothing valid matches; min / max / mean are unspecified there."""
+        torch = self.torch
+        opts = make_opts(strict, n_contigs, partition_mode=partition_mode)
+        dev = probe.start.device
+        plain = not min_overlap and probe_min is None and build_min is None
+        thr = None if plain else self._thresholds(probe, build, min_overlap, probe_min, build_min)
+        cols = []
+        for values, valid, ops in list(agg):
+            if values.dtype not in (torch.int64, torch.float64) or not values.is_cuda or not values.is_contiguous() or values.dim() != 1:
+                raise ValueError("value columns must be contiguous 1-D int64 or float64 CUDA tensors")
+            if valid is not None and (valid.dtype not in (torch.bool, torch.uint8) or not valid.is_cuda or not valid.is_contiguous()
+                                      or valid.shape != values.shape):
+                raise ValueError("validity columns must be contiguous bool / uint8 CUDA tensors of the value column's length")
+            cols.append((values, valid, AGG_I64 if values.dtype == torch.int64 else AGG_F64, agg_ops_mask(ops)))
+        lengths = {int(v.shape[0]) for v, _, _, _ in cols}
+        if len(lengths) > 1:
+            raise ValueError(f"the value columns of one call must have one length, got {sorted(lengths)}")
+        n_values = lengths.pop() if lengths else 0
+        kinds = {"sum": None, "min": None, "max": None, "mean": torch.float64, "count": torch.int64}
+        results = [{name: torch.zeros(probe.n, dtype=kinds[name] or values.dtype, device=dev) for name, bit in AGG_OPS.items() if ops & bit}
+                   for values, _, _, ops in cols]
+        if build.n == 0:
+            plain, thr = True, None                            # every count is 0 under either predicate
+        own = index is None
+        ix = self.engine.index_build_dev(build.as_c(), opts, plain) if own else index
+        try:
+            self.engine.overlap_agg_dev(
+                ix, probe.as_c(), opts, thr, n_values,
+                [(v.data_ptr() if n_values else 0, (m.data_ptr() if m is not None and n_values else 0), dt, ops) for v, m, dt, ops in cols],
+                [{name: (t.data_ptr() if probe.n else 0) for name, t in r.items()} for r in results])
+        finally:
+            if own:
+                ix.close()
+        return results
+
     # ---- join kinds: semi / anti (include/ivjoin.h: ivj_overlap_select_dev) -------------------------------
     def overlap_select(self, probe: DeviceSide, build: DeviceSide, strict: bool, n_contigs: int, mode, min_overlap: int = 0, probe_min=None,
                        build_min=None, index=None, out=None, partition_mode: int = 0):

@@ -27,7 +27,7 @@ from .constants import DEFAULT_INTERVAL_COLUMNS
 
 logger = logging.getLogger("polars_bio_amd")
 
-__all__ = ["overlap", "overlap_batches", "count_overlaps_batches", "nearest_batches", "nearest", "count_overlaps", "coverage", "mean_depth", "depth_summary", "merge", "cluster", "complement", "subtract",
+__all__ = ["overlap", "overlap_batches", "count_overlaps_batches", "nearest_batches", "nearest", "count_overlaps", "coverage", "mean_depth", "depth_summary", "merge", "cluster", "complement", "subtract", "map_overlaps",
            "set_intersect", "set_union", "set_difference", "set_symmetric_difference", "jaccard", "multi_intersect", "consensus",
            "FilterOp", "RangeOp", "OverlapOutputMode"]
 
@@ -1017,6 +1017,72 @@ def merge(
         for (name, ops), res in zip(spec, results):
             data.update(_agg_outputs(name, ops, t.schema.field(name).type, res))
     return A.from_arrow(pa.table(data), output_type, zero_based)
+
+
+def _map_engine():
+    eng = default_engine()
+    if not hasattr(eng, "overlap_agg"):
+        raise NotImplementedError(f"map_overlaps needs a single-device engine; the default engine is a {type(eng).__name__} "
+                                  "(several devices), which has no overlap aggregates")
+    return eng
+
+
+def map_overlaps(
+    df1,
+    df2,
+    agg: Union[dict, None] = None,
+    on_cols: Union[list, None] = None,
+    cols1: Union[list, None] = ["chrom", "start", "end"],
+    cols2: Union[list, None] = ["chrom", "start", "end"],
+    output_type: str = "polars.LazyFrame",
+    limit: Union[int, None] = None,
+    *,
+    min_overlap: Union[int, None] = None,
+    min_frac1: Union[float, None] = None,
+    min_frac2: Union[float, None] = None,
+):
+    """Summarise df2 value columns over the df2 intervals that overlap every df1 interval, as ``bedtools map -c/-o`` does:
+    ``pb.map_overlaps(genes, peaks, agg={"score": ["mean", "max"], "weight": "sum"})`` returns the df1 columns plus
+    ``score_mean``, ``score_max`` and ``weight_sum``, in the order of the dict and of each list, one row per df1 row in df1 row
+    order.  The pairs are reduced on the device: none is enumerated, none leaves it.
+
+    ``agg`` names df2 columns (signed integers, unsigned integers up to 32 bits, float32 or float64; not the interval or
+    ``on_cols`` columns).  Operations: ``sum`` (Int64 for integer columns, wrapping modulo 2^64; Float64 for float columns),
+    ``min`` / ``max`` (the column's own type), ``mean`` (Float64), ``count`` (Int64, the non-null values).  Null values are
+    skipped: ``sum`` and ``count`` over no value are 0, ``min`` / ``max`` / ``mean`` over none are null.  A NaN value makes the
+    ``sum`` and ``mean`` of its df1 row NaN; ``min`` / ``max`` skip NaNs unless every value is NaN.  Integer results are identical
+    from run to run; a float ``sum`` is evaluated in a fixed order and repeats bit for bit for the same rows in the same order.
+    An output name that is already a df1 column is a ValueError.
+
+    Which df2 rows count is what ``count_overlaps`` counts for the same call: the ``count`` of a column without nulls equals it.
+    ``on_cols``: only df2 rows of the df1 row's group of equal (chrom, on values) are reduced.  ``min_overlap`` / ``min_frac1`` /
+    ``min_frac2`` (keyword-only): only the df2 rows that pass the overlap thresholds of ``overlap`` (which see).  df1 rows with a
+    null chrom or on-value match nothing.
+
+    The call is eager whatever the ``output_type`` (``limit`` takes the head of the finished table, ``pyarrow.RecordBatchReader``
+    reads it).  Not offered: ``first`` / ``last`` / ``collapse`` / ``distinct`` / ``median``, string columns, the streaming and
+    Arrow-stream entries, several devices."""
+    mo, f1, f2 = _validate_overlap_thresholds(min_overlap, min_frac1, min_frac2)
+    on_cols = _validate_overlap_input(cols1, cols2, on_cols, ("_1", "_2"), output_type)
+    _check_on_cols_present(on_cols, df1, df2)
+    zero_based = validate_coordinate_systems(df1, df2)
+    c2 = list(DEFAULT_INTERVAL_COLUMNS if cols2 is None else cols2)
+    t1, t2, probe, build, n_contigs, _keys = _prepare(df1, df2, cols1, cols2, on_cols)
+    spec = _validate_agg(agg, t2, c2, on_cols)
+    for name, ops in spec:
+        for op in ops:
+            if f"{name}_{op}" in t1.column_names:
+                raise ValueError(f"agg: the output column '{name}_{op}' of column '{name}' collides with a column of df1")
+    eng = _map_engine()
+    pm, bm = _threshold_minima(probe, build, zero_based, f1, f2)
+    # count always travels along: it tells where min / max / mean are null
+    inputs = [(*_agg_input(t2, name, None), list(ops) + ["count"]) for name, ops in spec]
+    results = eng.overlap_agg(probe, build, strict=zero_based, n_contigs=n_contigs, agg=inputs, min_overlap=mo, probe_min=pm, build_min=bm)
+    table = t1
+    for (name, ops), res in zip(spec, results):
+        for out, column in _agg_outputs(name, ops, t2.schema.field(name).type, res).items():
+            table = table.append_column(out, column)
+    return _finish_eager(table, output_type, zero_based, limit)
 
 
 def depth(
