@@ -527,6 +527,33 @@ int ivj_overlap_agg_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, 
                         const ivj_thresholds* thr_dev /* NULL = plain predicate */, int64_t n_values, int32_t n_cols,
                         const ivj_agg_in* cols, const ivj_agg_out* agg_out);
 
+/* ---- permutation_test: overlap statistics of the probe side under circular shifts (regioneR circularRandomizeRegions) ---------------
+ * Half-open coordinates: hs = start - (Weak ? 1 : 0), he = end; contig c covers [0, contig_len[c]), contig_len[c] >= 1.
+ * offsets is an int32 table, row-major n_perm x opts->n_contigs, 0 <= offsets[p][c] < contig_len[c].
+ * A probe row takes part iff its contig is inside the dictionary and 0 <= hs < he <= contig_len[c]; any other row (no position,
+ * inverted, beyond the contig's end, outside the dictionary) contributes nothing to any permutation.  In permutation p a row is
+ *     s' = (hs + offsets[p][c]) mod L,  e' = s' + (he - hs)      (64-bit: e' reaches 2 L - 1)
+ * the single piece [s', e') when e' <= L, otherwise the two pieces [s', L) and [0, e' - L).  A piece matches a build row iff they
+ * share at least one position (the thresholded predicate with min_overlap = 1); build rows that cover no position never match.
+ *     n_pairs[p] = matches summed over the probe rows and their pieces -- a build row that reaches BOTH pieces of a wrapped row
+ *                  counts twice;
+ *     n_rows[p]  = probe rows with at least one match in any piece.
+ * A row of zero offsets gives the observed statistics.  Nothing per row or per pair exists in device memory, there is no atomic,
+ * and the results are identical from run to run.  Every opts->partition_mode routes to the one form.
+ * IVJ_EINVAL: n_perm < 1 or > 2^20, a NULL table (with n_contigs > 0) or a NULL output.
+ * IVJ_ESTATE: an index without lookup tables (with_end_order & 2).
+ * (New entries change no existing struct or signature: IVJ_ABI_VERSION stays.) */
+/* Host form: every pointer is host memory, n_pairs / n_rows hold n_perm entries.  Also IVJ_EINVAL for a contig_len < 1 or an
+ * offset outside [0, contig_len). */
+int ivj_permute_overlaps(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, const int32_t* contig_len,
+                         const int32_t* offsets, int64_t n_perm, int64_t* n_pairs, int64_t* n_rows);
+/* Device form on an index of ivj_index_build_dev (opts->n_contigs must be the index's): every pointer is device memory; enqueued on
+ * the context's stream.  Lengths and offsets are NOT validated: with values outside the ranges above the statistics are
+ * unspecified, but the kernel never reads outside the tables or the index whatever the values are (they only form 64-bit search
+ * targets that are clamped to the index's grid). */
+int ivj_permute_overlaps_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, const ivj_opts* opts, const int32_t* contig_len_dev,
+                             const int32_t* offsets_dev, int64_t n_perm, int64_t* n_pairs_dev, int64_t* n_rows_dev);
+
 /* ---- depth: run-length coverage blocks of one frame ------------------------------------------------------------------------------
  * The disjoint maximal runs of positions covered by the same number (>= 1) of the frame's rows, in (contig id, start) order: the
  * block form (chrom, start, end, coverage) of the reference's pb.depth (polars_bio/pileup_op.py:94-100), computed from an interval

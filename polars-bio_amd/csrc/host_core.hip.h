@@ -333,7 +333,7 @@ bool is_probe_kernel(const char* name) {
     return !std::strncmp(name, "overlap_", 8) || !std::strncmp(name, "count_overlaps", 14) || !std::strncmp(name, "nearest", 7) ||
            !std::strncmp(name, "materialize", 11) || !std::strncmp(name, "take", 4) || !std::strncmp(name, "coverage", 8) ||
            !std::strncmp(name, "subtract_", 9) || !std::strncmp(name, "cluster_", 8) || !std::strncmp(name, "part_scatter", 12) ||
-           !std::strncmp(name, "slice_", 6) || !std::strncmp(name, "cs_", 3);
+           !std::strncmp(name, "slice_", 6) || !std::strncmp(name, "cs_", 3) || !std::strncmp(name, "permute_overlaps", 16);
 }
 void t_begin(ivj_ctx* ctx, const char* name) {
     ctx->t_open = false;

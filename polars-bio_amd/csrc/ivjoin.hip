@@ -38,6 +38,7 @@
 #include "select.hip.h"
 #include "merge_agg.hip.h"
 #include "overlap_agg.hip.h"
+#include "permute.hip.h"
 
 using namespace ivj;
 
@@ -57,6 +58,7 @@ using namespace ivj;
 #include "host_thresh.hip.h"
 #include "host_select.hip.h"
 #include "host_overlap_agg.hip.h"
+#include "host_permute.hip.h"
 #include "host_stream.hip.h"
 #include "host_comm.hip.h"
 #include "host_group.hip.h"
@@ -1512,6 +1514,71 @@ int ivj_overlap_agg(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, 
     }
     if (rc != IVJ_OK) return rc;
     if (ce != hipSuccess) return fail(IVJ_EHIP, std::string("copies(overlap aggregates): ") + hipGetErrorString(ce));
+    return IVJ_OK;
+} IVJ_ABI_CATCH
+
+// ---------------------------------------------------------------- permutation_test: overlap statistics under circular shifts (permute.hip.h)
+// (the argument checks come before the context's: they need no device)
+
+int ivj_permute_overlaps_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, const ivj_opts* opts, const int32_t* contig_len_dev,
+                             const int32_t* offsets_dev, int64_t n_perm, int64_t* n_pairs_dev, int64_t* n_rows_dev) try {
+    IVJ_TRY(permute_check(opts, probe_dev, contig_len_dev, offsets_dev, n_perm, n_pairs_dev, n_rows_dev));
+    if (!ctx || !ix) return fail(IVJ_EINVAL, "ctx or index is NULL");
+    if (opts->n_contigs != ix->n_contigs) return fail(IVJ_EINVAL, "opts.n_contigs differs from the index's: the tables are laid out by it");
+    DeviceGuard g(ctx->device);
+    return permute_overlaps_dev(ctx, ix, probe_dev, opts, contig_len_dev, offsets_dev, n_perm, n_pairs_dev, n_rows_dev);
+} IVJ_ABI_CATCH
+
+int ivj_permute_overlaps(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, const int32_t* contig_len,
+                         const int32_t* offsets, int64_t n_perm, int64_t* n_pairs, int64_t* n_rows) try {
+    IVJ_TRY(permute_check(opts, probe, contig_len, offsets, n_perm, n_pairs, n_rows));
+    IVJ_TRY(check_side(build, "build"));
+    const size_t nc = (size_t)opts->n_contigs;
+    for (size_t c = 0; c < nc; ++c)
+        if (contig_len[c] < 1) return fail(IVJ_EINVAL, "contig_len[" + std::to_string(c) + "] < 1");
+    for (int64_t p = 0; p < n_perm; ++p) {
+        const int32_t* row = offsets + (size_t)p * nc;
+        for (size_t c = 0; c < nc; ++c)
+            if (row[c] < 0 || row[c] >= contig_len[c])
+                return fail(IVJ_EINVAL, "offsets[" + std::to_string(p) + "][" + std::to_string(c) + "] is outside [0, contig_len)");
+    }
+    if (!ctx) return fail(IVJ_EINVAL, "ctx is NULL");
+    if (probe->n == 0 || build->n == 0 || nc == 0) {
+        std::memset(n_pairs, 0, (size_t)n_perm * 8);
+        std::memset(n_rows, 0, (size_t)n_perm * 8);
+        return IVJ_OK;
+    }
+    DeviceGuard g(ctx->device);
+    DevSide dp, db;
+    IVJ_TRY(upload_side(ctx, build, db));
+    IVJ_TRY(upload_side(ctx, probe, dp));
+    IndexHolder h;
+    IVJ_TRY(index_build(ctx, &db.s, opts, 1, &h.ix));
+    PermPlan P;
+    IVJ_TRY(permute_plan(ctx, h.ix, &dp.s, opts, n_perm, P));
+    // the offsets travel in pieces of whole permutations (n_perm x n_contigs may be far more than one allocation should hold)
+    const size_t row_bytes = nc * 4;
+    int64_t rows_per_piece = (int64_t)(((size_t)64 << 20) / row_bytes);
+    rows_per_piece = rows_per_piece < 1 ? 1 : (rows_per_piece > n_perm ? n_perm : rows_per_piece);
+    const size_t len_bytes = align_up(row_bytes), out_bytes = align_up((size_t)n_perm * 8), piece_bytes = align_up((size_t)rows_per_piece * row_bytes);
+    DevBuf buf;
+    hipError_t e = hipMalloc(&buf.p, len_bytes + 2 * out_bytes + piece_bytes);
+    if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(permutation tables): ") + hipGetErrorString(e));
+    int32_t* d_len = (int32_t*)buf.p;
+    int64_t* d_pairs = (int64_t*)((char*)buf.p + len_bytes);
+    int64_t* d_rows = (int64_t*)((char*)buf.p + len_bytes + out_bytes);
+    int32_t* d_off = (int32_t*)((char*)buf.p + len_bytes + 2 * out_bytes);
+    HostXfer copy(ctx->stream, &ctx->xfer);
+    copy.h2d(d_len, contig_len, row_bytes);
+    for (int64_t p0 = 0; p0 < n_perm; p0 += rows_per_piece) {
+        // the copies and the launches are ordered by the stream: piece k + 1 overwrites the buffer after piece k's launches ran
+        const int64_t np = (n_perm - p0) < rows_per_piece ? (n_perm - p0) : rows_per_piece;
+        copy.h2d(d_off, offsets + (size_t)p0 * nc, (size_t)np * row_bytes);
+        IVJ_TRY(permute_run(ctx, h.ix, P, d_len, d_off, np, d_pairs + p0, d_rows + p0));
+    }
+    copy.d2h(n_pairs, d_pairs, (size_t)n_perm * 8);
+    copy.d2h(n_rows, d_rows, (size_t)n_perm * 8);
+    HIP_TRY(copy.finish());
     return IVJ_OK;
 } IVJ_ABI_CATCH
 

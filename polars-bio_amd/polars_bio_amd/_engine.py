@@ -35,7 +35,7 @@ ABI_SYMBOLS = [
     "ivj_subtract", "ivj_complement", "ivj_pieces_free", "ivj_subtract_dev",
     "ivj_merge", "ivj_merged_free", "ivj_cluster", "ivj_coverage", "ivj_cluster_dev", "ivj_merge_dev", "ivj_coverage_dev",
     "ivj_merge_agg", "ivj_merge_agg_free", "ivj_merge_agg_dev",
-    "ivj_overlap_agg", "ivj_overlap_agg_dev",
+    "ivj_overlap_agg", "ivj_overlap_agg_dev", "ivj_permute_overlaps", "ivj_permute_overlaps_dev",
     "ivj_overlap_bases", "ivj_overlap_bases_dev",
     "ivj_depth", "ivj_blocks_free", "ivj_depth_dev", "ivj_depth_summary", "ivj_depth_summary_dev",
     "ivj_setop", "ivj_regions_free", "ivj_set_stats", "ivj_setop_dev", "ivj_set_stats_dev",
@@ -270,6 +270,8 @@ def load_library() -> C.CDLL:
                                         C.POINTER(_AggOut), C.POINTER(C.c_int64)]
         L.ivj_overlap_agg.argtypes = [vp, P, P, O, T, C.c_int32, C.POINTER(_AggIn), C.POINTER(_AggOut)]
         L.ivj_overlap_agg_dev.argtypes = [vp, vp, P, O, T, C.c_int64, C.c_int32, C.POINTER(_AggIn), C.POINTER(_AggOut)]
+        L.ivj_permute_overlaps.argtypes = [vp, P, P, O, vp, vp, C.c_int64, vp, vp]
+        L.ivj_permute_overlaps_dev.argtypes = [vp, vp, P, O, vp, vp, C.c_int64, vp, vp]
         L.ivj_depth.argtypes = [vp, P, O, C.POINTER(_Blocks)]
         L.ivj_blocks_free.argtypes = [C.POINTER(_Blocks)]
         L.ivj_blocks_free.restype = None
@@ -977,6 +979,25 @@ class Engine:
         del keep_p, keep_b, keep_t
         return counts
 
+    def permute_overlaps(self, probe, build, strict: bool, n_contigs: int, contig_len, offsets, partition_mode: int = 0):
+        """pb.permutation_test (ivj_permute_overlaps): ``contig_len`` int32[n_contigs] (>= 1), ``offsets`` int32[n_perm, n_contigs]
+        with 0 <= offsets[p, c] < contig_len[c].  -> (n_pairs int64[n_perm], n_rows int64[n_perm]): per permutation the matches
+        summed over the circularly shifted probe rows and their pieces, and the probe rows with a match (include/ivjoin.h)."""
+        ps, keep_p = _host_side(*probe)
+        bs, keep_b = _host_side(*build)
+        o = make_opts(strict, n_contigs, partition_mode=partition_mode)
+        lens = np.ascontiguousarray(contig_len, dtype=np.int32).reshape(-1)
+        off = np.ascontiguousarray(offsets, dtype=np.int32)
+        if off.ndim != 2 or off.shape[1] != n_contigs or lens.shape[0] != n_contigs:
+            raise ValueError(f"offsets must be [n_perm, {n_contigs}] and contig_len [{n_contigs}], got {off.shape} and {lens.shape}")
+        n_perm = int(off.shape[0])
+        pairs, rows = np.zeros(n_perm, np.int64), np.zeros(n_perm, np.int64)
+        _check(self.L, self.L.ivj_permute_overlaps(self.h, C.byref(ps), C.byref(bs), C.byref(o), lens.ctypes.data if n_contigs else None,
+                                                   off.ctypes.data if off.size else None, n_perm, pairs.ctypes.data, rows.ctypes.data),
+               "ivj_permute_overlaps")
+        del keep_p, keep_b
+        return pairs, rows
+
     def _optional_thresholds(self, ps, bs, min_overlap, probe_min, build_min):
         """-> (pointer to an ivj_thresholds or None for the plain predicate, keep-alive)."""
         if not min_overlap and probe_min is None and build_min is None:
@@ -1311,6 +1332,13 @@ class Engine:
         k = int(thr.shape[0])
         _check(self.L, self.L.ivj_depth_summary_dev(self.h, ix.handle, C.byref(probe), C.byref(opts), thr.ctypes.data if k else None, k,
                                                      C.c_void_p(max_depth_ptr or None), C.c_void_p(bases_ge_ptr or None)), "ivj_depth_summary_dev")
+
+    def permute_overlaps_dev(self, ix: DeviceIndex, probe: _Side, opts: _Opts, contig_len_ptr: int, offsets_ptr: int, n_perm: int,
+                             n_pairs_ptr: int, n_rows_ptr: int):
+        """ivj_permute_overlaps_dev: device addresses of int32[n_contigs], int32[n_perm, n_contigs] and two int64[n_perm] outputs."""
+        _check(self.L, self.L.ivj_permute_overlaps_dev(self.h, ix.handle, C.byref(probe), C.byref(opts), C.c_void_p(contig_len_ptr or None),
+                                                       C.c_void_p(offsets_ptr or None), int(n_perm), C.c_void_p(n_pairs_ptr or None),
+                                                       C.c_void_p(n_rows_ptr or None)), "ivj_permute_overlaps_dev")
 
     def overlap_bases_dev(self, ix: DeviceIndex, probe: _Side, opts: _Opts, bases_ptr: int):
         _check(self.L, self.L.ivj_overlap_bases_dev(self.h, ix.handle, C.byref(probe), C.byref(opts), C.c_void_p(bases_ptr)),

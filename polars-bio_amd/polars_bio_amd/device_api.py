@@ -230,6 +230,34 @@ class DeviceJoin:
                 ix.close()
         return out
 
+    # ---- permutation_test (include/ivjoin.h: ivj_permute_overlaps_dev) ---------------------------------
+    def permute_overlaps(self, probe: DeviceSide, build: DeviceSide, strict: bool, n_contigs: int, contig_len, offsets, index=None,
+                         partition_mode: int = 0):
+        """Overlap statistics of ``probe`` under circular shifts: ``contig_len`` int32 CUDA tensor [n_contigs] (>= 1), ``offsets``
+        int32 CUDA tensor [n_perm, n_contigs] with 0 <= offsets[p, c] < contig_len[c] (NOT validated here: values outside give
+        unspecified statistics, never a read outside the tables).  -> (n_pairs, n_rows) int64 tensors of length n_perm."""
+        torch = self.torch
+        opts = make_opts(strict, n_contigs, partition_mode=partition_mode)
+        for t, what in ((contig_len, "contig_len"), (offsets, "offsets")):
+            if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous():
+                raise ValueError(f"{what} must be a contiguous int32 CUDA tensor")
+        if offsets.dim() != 2 or offsets.shape[1] != n_contigs or tuple(contig_len.shape) != (n_contigs,):
+            raise ValueError(f"offsets must be [n_perm, {n_contigs}] and contig_len [{n_contigs}]")
+        n_perm = int(offsets.shape[0])
+        pairs = torch.zeros(n_perm, dtype=torch.int64, device=probe.start.device)
+        rows = torch.zeros(n_perm, dtype=torch.int64, device=probe.start.device)
+        if n_perm and (probe.n == 0 or build.n == 0 or n_contigs == 0):
+            return pairs, rows
+        own = index is None
+        ix = self.engine.index_build_dev(build.as_c(), opts, True) if own else index
+        try:
+            self.engine.permute_overlaps_dev(ix, probe.as_c(), opts, contig_len.data_ptr(), offsets.data_ptr(), n_perm, pairs.data_ptr(),
+                                             rows.data_ptr())
+        finally:
+            if own:
+                ix.close()
+        return pairs, rows
+
     # ---- map_overlaps (include/ivjoin.h: ivj_overlap_agg_dev) ------------------------------------------
     def overlap_agg(self, probe: DeviceSide, build: DeviceSide, strict: bool, n_contigs: int, agg, min_overlap: int = 0, probe_min=None,
                     build_min=None, index=None, partition_mode: int = 0):

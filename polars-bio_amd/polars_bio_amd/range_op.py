@@ -1085,6 +1085,155 @@ def map_overlaps(
     return _finish_eager(table, output_type, zero_based, limit)
 
 
+PERMUTATION_MAX = (1 << 20) - 1          # the engine takes 2^20 offset rows per call, one of them the observed (all-zero) row
+
+
+def _permutation_engine():
+    eng = default_engine()
+    if not hasattr(eng, "permute_overlaps"):
+        raise NotImplementedError(f"permutation_test needs a single-device engine; the default engine is a {type(eng).__name__} "
+                                  "(several devices), which has no permutation kernel")
+    return eng
+
+
+def _genome_lengths(genome):
+    """-> (names sorted, int64 lengths in that order) of a {contig: length} dict or a two-column (name, length) frame."""
+    if not isinstance(genome, dict):
+        t = A.to_arrow(genome)
+        if t.num_columns != 2:
+            raise ValueError(f"genome must be a dict or a frame of two columns (contig, length), got {t.num_columns} columns")
+        names, lens = t.column(0).to_pylist(), t.column(1).to_pylist()
+        if len(set(names)) != len(names):
+            raise ValueError("genome names a contig twice")
+        genome = dict(zip(names, lens))
+    if not genome:
+        raise ValueError("genome is empty")
+    for k, v in genome.items():
+        if k is None or v is None or isinstance(v, bool) or int(v) != v or not 1 <= int(v) <= 2 ** 31 - 1:
+            raise ValueError(f"genome: the length of contig {k!r} must be an integer in [1, 2^31 - 1], got {v!r}")
+    genome = {str(k): int(v) for k, v in genome.items()}
+    names = sorted(genome)
+    return names, np.array([genome[k] for k in names], np.int64)
+
+
+def permutation_offsets(genome, n_perm: int, seed: int = 0):
+    """The offset table ``permutation_test`` draws for (genome, n_perm, seed): -> (names, offsets int64 [n_perm, len(names)]);
+    column j belongs to names[j] = sorted(genome)[j]."""
+    names, lengths = _genome_lengths(genome)
+    rng = np.random.default_rng(seed)
+    return names, rng.integers(0, lengths[None, :], size=(n_perm, len(names)))
+
+
+def permutation_test(
+    df1,
+    df2,
+    genome,
+    n_perm: int = 1000,
+    seed: int = 0,
+    on_cols: Union[list, None] = None,
+    cols1: Union[list, None] = ["chrom", "start", "end"],
+    cols2: Union[list, None] = ["chrom", "start", "end"],
+    output: str = "summary",
+    output_type: str = "polars.LazyFrame",
+    offsets=None,
+):
+    """Is the overlap of df1 with df2 more than chance?  A circular-shift permutation test (regioneR's
+    ``circularRandomizeRegions``, a loop over ``bedtools shuffle | bedtools intersect``): in every permutation all df1 intervals of
+    a contig move by one random offset along it, wrapping at its end; df2 stays.  Two statistics are recounted per permutation on
+    the device, where df1 stays in registers and nothing per row or per pair exists in memory:
+
+    * ``n_pairs``: the overlapping (df1, df2) pairs.  A df1 interval that wraps is two pieces, [s', L) and [0, e' - L); a df2
+      interval that reaches both pieces counts TWICE;
+    * ``n_rows``: the df1 intervals that overlap at least one df2 interval.
+
+    "Overlap" means sharing at least one position (``min_overlap = 1``); intervals that cover no position match nothing.  The
+    observed values are the same computation with every offset 0.
+
+    ``genome``: {contig: length} or a two-column frame (contig, length); contig c covers [0, length) in half-open coordinates.
+    Every contig of df1 must be in it, and every df1 interval with a chrom must lie inside its contig and cover a position
+    (ValueError otherwise, naming the first row that does not).  df1 rows with a null chrom or a null on-value take no part.
+
+    Offsets, so that a result can be reproduced outside the library::
+
+        names = sorted(genome); rng = np.random.default_rng(seed)
+        off = rng.integers(0, lengths[None, :], size=(n_perm, len(names)))       # column j belongs to names[j]
+
+    ``offsets=`` gives that table explicitly ([n_perm, len(genome)], 0 <= offset < length) and overrides ``seed`` and ``n_perm``.
+    ``on_cols``: only df2 rows of the df1 row's group of equal (chrom, on values) count; every group of a chrom moves by that
+    chrom's offset.
+
+    ``output="null"``: the table (permutation, n_pairs, n_rows), one row per permutation.  ``output="summary"``: one row per
+    statistic with ``statistic, observed, n_perm, null_mean, null_sd`` (ddof = 1, null when n_perm < 2), ``z_score`` (null when
+    the sd is 0 or null), ``p_greater = (1 + #{null >= observed}) / (n_perm + 1)`` and ``p_less`` likewise with <=.
+
+    The call is eager.  Not offered: a bases or jaccard statistic, thresholds other than the implied ``min_overlap = 1``,
+    non-circular randomisation (``shuffle`` with exclusion masks), per-group offsets, the streaming and Arrow-stream entries,
+    several devices."""
+    if output not in ("summary", "null"):
+        raise ValueError(f"output must be 'summary' or 'null', got {output!r}")
+    on_cols = _validate_overlap_input(cols1, cols2, on_cols, ("_1", "_2"), output_type)
+    _check_on_cols_present(on_cols, df1, df2)
+    names, lengths = _genome_lengths(genome)
+    if offsets is None:
+        if isinstance(n_perm, bool) or int(n_perm) != n_perm or not 1 <= int(n_perm) <= PERMUTATION_MAX:
+            raise ValueError(f"n_perm must be an integer in [1, {PERMUTATION_MAX}], got {n_perm!r}")
+        off = np.random.default_rng(seed).integers(0, lengths[None, :], size=(int(n_perm), len(names)))
+    else:
+        off = np.asarray(offsets)
+        if off.ndim != 2 or off.shape[1] != len(names) or not 1 <= off.shape[0] <= PERMUTATION_MAX or off.dtype.kind not in "iu":
+            raise ValueError(f"offsets must be an integer array of shape [1 .. {PERMUTATION_MAX}, {len(names)}], got {off.dtype} {off.shape}")
+        off = off.astype(np.int64)
+        if (off < 0).any() or (off >= lengths[None, :]).any():
+            raise ValueError("offsets must satisfy 0 <= offsets[p, j] < length of sorted(genome)[j]")
+    n_perm = int(off.shape[0])
+    zero_based = validate_coordinate_systems(df1, df2)
+    c1 = list(DEFAULT_INTERVAL_COLUMNS if cols1 is None else cols1)
+    t1, _t2, probe, build, n_contigs, keys = _prepare(df1, df2, cols1, cols2, on_cols)
+    # genome column of every chrom id of the shared dictionary (-1: the genome does not name it)
+    chroms = [None if x is None else str(x) for x in keys[4].to_pylist()]
+    col_of = {k: j for j, k in enumerate(names)}
+    chrom_col = np.array([col_of.get(k, -1) for k in chroms] + [-1], np.int64)              # (the last entry answers id -1)
+    ch1 = keys[1]
+    if len(ch1):
+        absent = (ch1 >= 0) & (chrom_col[ch1] < 0)
+        if absent.any():
+            i = int(np.flatnonzero(absent)[0])
+            raise ValueError(f"df1 row {i}: contig {chroms[ch1[i]]!r} is not in genome")
+        hs = probe[1].astype(np.int64) - (0 if zero_based else 1)
+        he = probe[2].astype(np.int64)
+        bad = (ch1 >= 0) & ~((0 <= hs) & (hs < he) & (he <= lengths[np.maximum(chrom_col[ch1], 0)]))
+        if bad.any():
+            i = int(np.flatnonzero(bad)[0])
+            raise ValueError(f"df1 row {i}: {c1[1]}={int(probe[1][i])}, {c1[2]}={int(probe[2][i])} does not lie inside contig "
+                             f"{chroms[ch1[i]]!r} of length {int(lengths[chrom_col[ch1[i]]])} or covers no position")
+    eng = _permutation_engine()
+    # the engine's contigs are chrom ids, or with on_cols group ids, each with its chrom's column; contigs the genome does not name
+    # hold no df1 row: any length does
+    group_chrom = np.arange(n_contigs, dtype=np.int64) if keys[5] is None else np.asarray(keys[5], np.int64)[:n_contigs]
+    gcol = chrom_col[group_chrom] if len(chroms) else np.full(n_contigs, -1, np.int64)
+    have = gcol >= 0
+    lens = np.where(have, lengths[np.maximum(gcol, 0)], 1).astype(np.int32)
+    table = np.zeros((n_perm + 1, n_contigs), np.int32)                                      # row 0: the observed statistics
+    table[1:, have] = off[:, gcol[have]]
+    pairs, rows = eng.permute_overlaps(probe, build, strict=zero_based, n_contigs=n_contigs, contig_len=lens, offsets=table)
+    pairs, rows = np.asarray(pairs, np.int64), np.asarray(rows, np.int64)
+    if output == "null":
+        out = pa.table({"permutation": pa.array(np.arange(n_perm, dtype=np.int64)), "n_pairs": pa.array(pairs[1:]), "n_rows": pa.array(rows[1:])})
+        return _finish_eager(out, output_type, zero_based, None)
+    data = {k: [] for k in ("statistic", "observed", "n_perm", "null_mean", "null_sd", "z_score", "p_greater", "p_less")}
+    for name, v in (("n_pairs", pairs), ("n_rows", rows)):
+        obs, null = int(v[0]), v[1:].astype(np.float64)
+        mean = float(null.mean())
+        sd = float(null.std(ddof=1)) if n_perm >= 2 else None
+        for k, x in (("statistic", name), ("observed", obs), ("n_perm", n_perm), ("null_mean", mean), ("null_sd", sd),
+                     ("z_score", (obs - mean) / sd if sd else None),
+                     ("p_greater", (1 + int((v[1:] >= obs).sum())) / (n_perm + 1)), ("p_less", (1 + int((v[1:] <= obs).sum())) / (n_perm + 1))):
+            data[k].append(x)
+    types = {"statistic": pa.large_string(), "observed": pa.int64(), "n_perm": pa.int64()}
+    out = pa.table({k: pa.array(x, type=types.get(k, pa.float64())) for k, x in data.items()})
+    return _finish_eager(out, output_type, zero_based, None)
+
+
 def depth(
     df,
     cols: Union[list, None] = ["chrom", "start", "end"],
