@@ -442,6 +442,22 @@ int ivj_coverage_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, con
  * an index without the end order is completed here.  partition_mode 1 buckets the probes first; 0 and 2 run in probe order. */
 int ivj_overlap_bases_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, const ivj_opts* opts, int64_t* bases_dev);
 
+/* pb.depth_profile: every window row cut into n_bins bins, per bin the positions it shares with each build interval of the window's
+ * contig, summed over the build intervals -- ivj_overlap_bases of the bin as a probe row -- as a row-major windows->n x n_bins
+ * Int64 matrix (caller buffer).  A window covers S .. S + L - 1 ([s, e) Strict: L = e - s, [s, e] Weak: L = e - s + 1); its bin
+ * edges in half-open position space are x_j = S + floor(j L / n_bins), j = 0 .. n_bins, bin j = [x_j, x_{j+1}): lengths differ by at
+ * most one and sum to L, so a row of the matrix sums to the window's ivj_overlap_bases.  L <= 0: every bin is empty; L < n_bins:
+ * some are; an empty bin has 0.  reverse (one byte per window, NULL: none set): a row whose byte is non-zero comes back right to
+ * left, column j holding bin n_bins - 1 - j.  1 <= n_bins <= 4096, anything else is IVJ_EINVAL.  Contig ids outside [0, n_contigs)
+ * match nothing; build rows that cover no position contribute nothing.  opts->partition_mode is ignored: the windows are read in
+ * their own order.  Exact integers; the result is identical from run to run. */
+int ivj_depth_profile(ivj_ctx* ctx, const ivj_side* windows, const uint8_t* reverse, int32_t n_bins, const ivj_side* build,
+                      const ivj_opts* opts, int64_t* bases);
+/* The same on an index already in HBM, windows / reverse / bases in device memory.  An index without the end order or the position
+ * sums is completed on its first call, as by ivj_overlap_bases_dev.  Runs on the context's stream; nothing is synchronised. */
+int ivj_depth_profile_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* windows_dev, const uint8_t* reverse_dev, int32_t n_bins,
+                          const ivj_opts* opts, int64_t* bases_dev);
+
 /* ---- merge with aggregates: a value column reduced per merged interval (bedtools merge -c / -o) -----------------------------------
  * ivj_merge plus, per value column, any of count / sum / min / max / mean over the rows merged into each interval.  The merged
  * table is exactly ivj_merge's for the same input; n_cols value columns share one cluster sweep.  Per column and cluster, over the

@@ -31,6 +31,7 @@
 #include "group.hip.h"
 #include "depth.hip.h"
 #include "depth_sum.hip.h"
+#include "depth_profile.hip.h"
 #include "depth_query.hip.h"
 #include "setop.hip.h"
 #include "multi.hip.h"
@@ -52,6 +53,7 @@ using namespace ivj;
 #include "host_merge_agg.hip.h"
 #include "host_depth.hip.h"
 #include "host_depth_sum.hip.h"
+#include "host_depth_profile.hip.h"
 #include "host_depth_query.hip.h"
 #include "host_setop.hip.h"
 #include "host_multi.hip.h"
@@ -828,6 +830,32 @@ int ivj_overlap_bases(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build
     copy.d2h(bases, out.p, (size_t)probe->n * 8);
     HIP_TRY(copy.finish());
     return IVJ_OK;
+} IVJ_ABI_CATCH
+
+// ---------------------------------------------------------------- depth profile (per-bin base sums of every window row)
+
+int ivj_depth_profile_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* windows_dev, const uint8_t* reverse_dev, int32_t n_bins,
+                          const ivj_opts* opts, int64_t* bases_dev) try {
+    if (!ctx || !ix) return fail(IVJ_EINVAL, "ctx or index is NULL");
+    IVJ_TRY(check_opts(opts));
+    IVJ_TRY(check_side(windows_dev, "windows"));
+    IVJ_TRY(depth_profile_check(n_bins));
+    if (windows_dev->n > 0 && !bases_dev) return fail(IVJ_EINVAL, "bases is NULL");
+    DeviceGuard g(ctx->device);
+    return depth_profile_dev(ctx, ix, windows_dev, reverse_dev, n_bins, opts, bases_dev);
+} IVJ_ABI_CATCH
+
+int ivj_depth_profile(ivj_ctx* ctx, const ivj_side* windows, const uint8_t* reverse, int32_t n_bins, const ivj_side* build,
+                      const ivj_opts* opts, int64_t* bases) try {
+    if (!ctx) return fail(IVJ_EINVAL, "ctx is NULL");
+    IVJ_TRY(check_opts(opts));
+    IVJ_TRY(check_side(windows, "windows"));
+    IVJ_TRY(check_side(build, "build"));
+    IVJ_TRY(depth_profile_check(n_bins));
+    if (windows->n == 0) return IVJ_OK;
+    if (!bases) return fail(IVJ_EINVAL, "bases is NULL");
+    DeviceGuard g(ctx->device);
+    return depth_profile_host(ctx, windows, reverse, n_bins, build, opts, bases);
 } IVJ_ABI_CATCH
 
 // ---------------------------------------------------------------- depth (run-length coverage blocks)

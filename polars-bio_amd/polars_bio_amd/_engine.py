@@ -36,7 +36,7 @@ ABI_SYMBOLS = [
     "ivj_merge", "ivj_merged_free", "ivj_cluster", "ivj_coverage", "ivj_cluster_dev", "ivj_merge_dev", "ivj_coverage_dev",
     "ivj_merge_agg", "ivj_merge_agg_free", "ivj_merge_agg_dev",
     "ivj_overlap_agg", "ivj_overlap_agg_dev", "ivj_permute_overlaps", "ivj_permute_overlaps_dev",
-    "ivj_overlap_bases", "ivj_overlap_bases_dev",
+    "ivj_overlap_bases", "ivj_overlap_bases_dev", "ivj_depth_profile", "ivj_depth_profile_dev",
     "ivj_depth", "ivj_blocks_free", "ivj_depth_dev", "ivj_depth_summary", "ivj_depth_summary_dev",
     "ivj_setop", "ivj_regions_free", "ivj_set_stats", "ivj_setop_dev", "ivj_set_stats_dev",
     "ivj_multi_inter", "ivj_segments_free", "ivj_multi_inter_dev",
@@ -56,6 +56,7 @@ ABI_VERSION = 6            # include/ivjoin.h: IVJ_ABI_VERSION (struct layouts a
 STREAM_OVERLAP, STREAM_COUNT, STREAM_NEAREST = 0, 1, 2
 # ivj_opts.nearest_ignore: the candidate classes a nearest call leaves out (rows before / after the probe; overlapping rows always count)
 NEAREST_IGNORE_LEFT, NEAREST_IGNORE_RIGHT = 1, 2
+DEPTH_PROFILE_MAX_BINS = 4096        # include/ivjoin.h: ivj_depth_profile accepts 1 .. this many bins
 
 # the operations of ivj_setop / ivj_setop_dev (include/ivjoin.h: IVJ_SETOP_*)
 SETOP_INTERSECTION, SETOP_UNION, SETOP_DIFFERENCE, SETOP_SYMMETRIC_DIFFERENCE = 0, 1, 2, 3
@@ -289,6 +290,8 @@ def load_library() -> C.CDLL:
         L.ivj_coverage_dev.argtypes = [vp, vp, P, O, vp]
         L.ivj_overlap_bases.argtypes = [vp, P, P, O, vp]
         L.ivj_overlap_bases_dev.argtypes = [vp, vp, P, O, vp]
+        L.ivj_depth_profile.argtypes = [vp, P, vp, C.c_int32, P, O, vp]
+        L.ivj_depth_profile_dev.argtypes = [vp, vp, P, vp, C.c_int32, O, vp]
         L.ivj_depth_summary.argtypes = [vp, P, P, O, vp, C.c_int32, vp, vp]
         L.ivj_depth_summary_dev.argtypes = [vp, vp, P, O, vp, C.c_int32, vp, vp]
         L.ivj_stream_open.argtypes = [vp, P, O, C.c_int, C.c_int64, C.POINTER(vp)]
@@ -893,6 +896,26 @@ class Engine:
         del keep_p, keep_b
         return bases
 
+    def depth_profile(self, windows, reverse, n_bins: int, build, strict: bool, n_contigs: int) -> np.ndarray:
+        """pb.depth_profile: every window row cut into n_bins bins (edges S + floor(j L / n_bins)), per bin the positions shared with
+        each build row of the window's contig, summed -> int64 (n, n_bins), window order.  ``reverse``: None or one flag per window;
+        a flagged row comes back right to left."""
+        ws, keep_w = _host_side(*windows)
+        bs, keep_b = _host_side(*build)
+        o = make_opts(strict, n_contigs)
+        rev = None
+        if reverse is not None:
+            rev = np.ascontiguousarray(np.asarray(reverse).astype(bool).astype(np.uint8))
+            if rev.shape != (ws.n,):
+                raise ValueError(f"reverse must hold one flag per window ({ws.n}), got shape {rev.shape}")
+        n_bins = int(n_bins)
+        # a bin count the entry refuses gets no matrix: the entry checks n_bins before it looks at the output
+        bases = np.empty((ws.n, n_bins if 1 <= n_bins <= DEPTH_PROFILE_MAX_BINS else 0), np.int64)
+        _check(self.L, self.L.ivj_depth_profile(self.h, C.byref(ws), rev.ctypes.data if rev is not None and ws.n else None, int(n_bins),
+                                                 C.byref(bs), C.byref(o), bases.ctypes.data if bases.size else None), "ivj_depth_profile")
+        del keep_w, keep_b
+        return bases
+
     def depth_summary(self, probe, build, strict: bool, n_contigs: int, thresholds=(1,), partition_mode: int = 0, want_max: bool = True):
         """pb.depth_summary: -> (max_depth int32[n], bases_ge int64[K, n]): per probe row the largest number of build rows of its
         contig that cover one of its positions, and per threshold T = thresholds[k] the number of its positions covered by at
@@ -1343,6 +1366,11 @@ class Engine:
     def overlap_bases_dev(self, ix: DeviceIndex, probe: _Side, opts: _Opts, bases_ptr: int):
         _check(self.L, self.L.ivj_overlap_bases_dev(self.h, ix.handle, C.byref(probe), C.byref(opts), C.c_void_p(bases_ptr)),
                "ivj_overlap_bases_dev")
+
+    def depth_profile_dev(self, ix: DeviceIndex, windows: _Side, reverse_ptr: int, n_bins: int, opts: _Opts, bases_ptr: int):
+        """reverse_ptr: device address of one byte per window (0 = NULL: none reversed); bases_ptr: row-major int64[n, n_bins]."""
+        _check(self.L, self.L.ivj_depth_profile_dev(self.h, ix.handle, C.byref(windows), C.c_void_p(reverse_ptr or None), int(n_bins),
+                                                     C.byref(opts), C.c_void_p(bases_ptr or None)), "ivj_depth_profile_dev")
 
     def count_overlaps_dev(self, ix: DeviceIndex, probe: _Side, opts: _Opts, counts_ptr: int):
         _check(self.L, self.L.ivj_count_overlaps_dev(self.h, ix.handle, C.byref(probe), C.byref(opts),

@@ -366,6 +366,35 @@ class DeviceJoin:
                 ix.close()
         return bases
 
+    def depth_profile(self, windows: DeviceSide, build: DeviceSide, strict: bool, n_contigs: int, n_bins: int, reverse=None,
+                      index=None, out=None):
+        """Every window row cut into ``n_bins`` bins (edges S + floor(j L / n_bins) over the row's L positions), per bin the
+        positions shared with each build row of the window's contig, summed -> int64 tensor (windows.n, n_bins) in HBM; a row
+        sums to its ``overlap_bases``.  ``reverse``: None or a bool / uint8 CUDA tensor of windows.n flags, a flagged row comes
+        back right to left.  ``index`` / ``out`` as in ``overlap_bases`` (``out``: contiguous int64 of that shape)."""
+        torch = self.torch
+        n_bins = int(n_bins)
+        opts = make_opts(strict, n_contigs)
+        dev = windows.start.device
+        rev = None
+        if reverse is not None:
+            rev = reverse.to(torch.uint8) if reverse.dtype == torch.bool else reverse
+            if rev.dtype != torch.uint8 or tuple(rev.shape) != (windows.n,) or not rev.is_contiguous() or rev.device != dev:
+                raise ValueError("reverse must be a contiguous bool / uint8 tensor of windows.n elements on the windows' device")
+        if out is not None and (out.dtype != torch.int64 or tuple(out.shape) != (windows.n, n_bins) or not out.is_contiguous()):
+            raise ValueError("out must be a contiguous int64 tensor of shape (windows.n, n_bins)")
+        own = index is None
+        ix = self.engine.index_build_dev(build.as_c(), opts, False) if own else index
+        try:
+            bases = out if out is not None else torch.empty((windows.n, max(n_bins, 0)), dtype=torch.int64, device=dev)
+            # (a tensor without elements has no address: the entry still checks n_bins, and refuses a NULL output only with rows)
+            self.engine.depth_profile_dev(ix, windows.as_c(), rev.data_ptr() if rev is not None and windows.n else 0, n_bins, opts,
+                                          bases.data_ptr() if bases.numel() else 0)
+        finally:
+            if own:
+                ix.close()
+        return bases
+
     def depth_summary(self, probe: DeviceSide, build: DeviceSide, strict: bool, n_contigs: int, thresholds=(1,), index=None,
                       out_max=None, out_bases=None, partition_mode: int = 0):
         """Per probe row the maximum depth of the build side under it and, per threshold T, its positions covered at least T deep

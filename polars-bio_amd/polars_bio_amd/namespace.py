@@ -14,6 +14,7 @@ from . import range_op
 _ALIASES = {
     "overlap": (range_op.overlap, True), "nearest": (range_op.nearest, True), "count_overlaps": (range_op.count_overlaps, True),
     "coverage": (range_op.coverage, True), "mean_depth": (range_op.mean_depth, True), "depth_summary": (range_op.depth_summary, True),
+    "depth_profile": (range_op.depth_profile, True),
     "subtract": (range_op.subtract, True), "map_overlaps": (range_op.map_overlaps, True),
     "permutation_test": (range_op.permutation_test, True),
     "merge": (range_op.merge, False), "depth": (range_op.depth, False), "cluster": (range_op.cluster, False), "complement": (range_op.complement, False),

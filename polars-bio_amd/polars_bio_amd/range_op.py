@@ -21,13 +21,13 @@ import pyarrow as pa
 import pyarrow.compute as pc
 
 from . import _arrow as A
-from ._engine import EngineError, default_engine
+from ._engine import DEPTH_PROFILE_MAX_BINS, EngineError, default_engine
 from ._metadata import validate_coordinate_system_single, validate_coordinate_systems
 from .constants import DEFAULT_INTERVAL_COLUMNS
 
 logger = logging.getLogger("polars_bio_amd")
 
-__all__ = ["overlap", "overlap_batches", "count_overlaps_batches", "nearest_batches", "nearest", "count_overlaps", "coverage", "mean_depth", "depth_summary", "merge", "cluster", "complement", "subtract", "map_overlaps",
+__all__ = ["overlap", "overlap_batches", "count_overlaps_batches", "nearest_batches", "nearest", "count_overlaps", "coverage", "mean_depth", "depth_profile", "depth_summary", "merge", "cluster", "complement", "subtract", "map_overlaps",
            "set_intersect", "set_union", "set_difference", "set_symmetric_difference", "jaccard", "multi_intersect", "consensus",
            "FilterOp", "RangeOp", "OverlapOutputMode"]
 
@@ -827,6 +827,135 @@ def mean_depth(
     t = t1.append_column("bases", pa.array(bases, type=pa.int64()))
     t = t.append_column("mean_depth", pa.array(mean, type=pa.float64(), mask=~has_positions))
     return A.from_arrow(t, output_type, zero_based)
+
+
+_PROFILE_ANCHORS = ("start", "end", "center")
+
+
+def profile_windows(start, end, zero_based: bool, anchor=None, upstream: int = 0, downstream: int = 0, is_minus=None):
+    """The window of every df1 row of ``depth_profile`` -> (window start, window end) as int64 arrays in the frames' own coordinate
+    convention.  ``anchor=None``: the row itself.  Otherwise, in half-open position space with S the row's first position and L its
+    number of positions, the window is [a - upstream, a + downstream) around a = S ("start"), S + L ("end": one past the last
+    position) or S + L // 2 ("center"); for a row flagged in ``is_minus`` "start" / "end" and upstream / downstream swap.  A row
+    that covers no position (end before start) reads as L = 0 from its start: all three anchors are S."""
+    s = np.asarray(start, np.int64)
+    e = np.asarray(end, np.int64)
+    if anchor is None:
+        return s.copy(), e.copy()
+    w = 0 if zero_based else 1
+    length = np.maximum(e - s + w, 0)
+    minus = np.zeros(len(s), bool) if is_minus is None else np.asarray(is_minus, bool)
+    if anchor == "center":
+        a = s + length // 2
+    else:
+        a = np.where((anchor == "end") != minus, s + length, s)
+    lo = a - np.where(minus, np.int64(downstream), np.int64(upstream))
+    hi = a + np.where(minus, np.int64(upstream), np.int64(downstream))
+    return lo, hi - w
+
+
+def profile_bin_lengths(w_start, w_end, zero_based: bool, n_bins: int, reverse=None) -> np.ndarray:
+    """Positions of every bin of every window, int64 (n, n_bins): bin j of a window of L positions is
+    [floor(j L / n_bins), floor((j + 1) L / n_bins)) from its first position (L <= 0: every bin is empty); the rows flagged in
+    ``reverse`` right to left."""
+    length = np.maximum(np.asarray(w_end, np.int64) - np.asarray(w_start, np.int64) + (0 if zero_based else 1), 0)
+    edges = length[:, None] * np.arange(n_bins + 1, dtype=np.int64)[None, :] // np.int64(n_bins)      # j L < 2^13 x 2^32
+    lens = np.diff(edges, axis=1)
+    if reverse is not None:
+        rev = np.asarray(reverse, bool)
+        lens[rev] = lens[rev, ::-1]
+    return lens
+
+
+def depth_profile(
+    df1,
+    df2,
+    n_bins: int = 100,
+    anchor: Union[str, None] = None,
+    upstream: int = 0,
+    downstream: int = 0,
+    direction_col: Union[str, None] = None,
+    on_cols: Union[list, None] = None,
+    cols1: Union[list, None] = ["chrom", "start", "end"],
+    cols2: Union[list, None] = ["chrom", "start", "end"],
+    output: str = "mean",
+    output_type: str = "polars.LazyFrame",
+):
+    """Binned depth of df2 across every df1 row: a rows x ``n_bins`` matrix for a heat map or an average profile (deepTools
+    ``computeMatrix``, ngs.plot, ``bedtools makewindows -n`` + ``coverage -mean``), made on the device from the window of each row.
+
+    The window of a df1 row of L positions from S is cut at S + floor(j L / n_bins), j = 0 .. n_bins: bin lengths differ by at
+    most one and sum to L.  Per bin, ``bases`` = the positions it shares with each df2 interval of the row's contig, summed over
+    the df2 intervals -- what ``mean_depth`` gives for the bin as a df1 row, so a row of the matrix sums to the window's
+    ``mean_depth`` ``bases``.  A window with L < n_bins has empty bins, one with L <= 0 only empty bins: ``bases`` 0, mean null.
+
+    ``anchor=None`` (scale-regions): the window is the df1 row itself; ``upstream`` / ``downstream`` must be 0.
+    ``anchor`` = ``"start"`` | ``"end"`` | ``"center"`` (reference-point): the window is [a - upstream, a + downstream) in
+    half-open position space, a = the row's first position, one past its last position, or S + L // 2 (a row that covers no
+    position reads as L = 0: a = S for every anchor); ``upstream`` and
+    ``downstream`` are ints >= 0 with ``upstream + downstream >= 1``.  Windows are computed in int64; one that leaves the int32
+    range is a ValueError naming the first such row.  Negative coordinates are legal, the depth there is 0.
+    ``direction_col`` names a df1 column of "+" / "-" (any other value or a null reads as "+"): a "-" row is read along its
+    strand, i.e. its profile comes back right to left, and in reference-point mode "start" / "end" and ``upstream`` /
+    ``downstream`` swap for it -- a minus gene's TSS is its end.
+
+    ``output="mean"``: Float64 bases / bin length, null for an empty bin; ``output="bases"``: Int64.  The result is df1's columns
+    plus one column ``profile`` of Arrow ``fixed_size_list<...>[n_bins]`` laid over the matrix, df1 row order kept;
+    ``output_type="numpy.ndarray"`` returns the bare (n, n_bins) matrix (NaN for null in the mean form).  0-based frames are
+    half-open, 1-based frames closed.  Rows of df2 that cover no position and rows with a null chrom share nothing.
+    ``on_cols``: only df2 intervals of the df1 row's group of equal (chrom, on values) count; a null on-value matches nothing.
+
+    Eager.  Not covered: a value / weight column on df2 (bedGraph signal), streaming inputs or outputs, several devices, per-bin
+    statistics other than the sum / mean."""
+    on_cols = _validate_overlap_input(cols1, cols2, on_cols, ("_1", "_2"), "pyarrow.Table" if output_type == "numpy.ndarray" else output_type)
+    if isinstance(n_bins, (bool, np.bool_)) or not isinstance(n_bins, (int, np.integer)) or not 1 <= int(n_bins) <= DEPTH_PROFILE_MAX_BINS:
+        raise ValueError(f"n_bins must be an int in 1 .. {DEPTH_PROFILE_MAX_BINS}, got {n_bins!r}")
+    n_bins = int(n_bins)
+    if output not in ("mean", "bases"):
+        raise ValueError(f"output must be 'mean' or 'bases', got {output!r}")
+    if anchor is not None and anchor not in _PROFILE_ANCHORS:
+        raise ValueError(f"anchor must be None or one of {_PROFILE_ANCHORS}, got {anchor!r}")
+    for name, v in (("upstream", upstream), ("downstream", downstream)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= 0xffffffff:
+            raise ValueError(f"{name} must be an int in 0 .. 2^32 - 1, got {v!r}")
+    upstream, downstream = int(upstream), int(downstream)
+    if anchor is None and (upstream or downstream):
+        raise ValueError(f"upstream / downstream need an anchor ('start', 'end' or 'center'), got upstream={upstream}, downstream={downstream} with anchor=None")
+    if anchor is not None and upstream + downstream < 1:
+        raise ValueError(f"anchor={anchor!r} needs upstream + downstream >= 1, got {upstream} + {downstream}")
+    if direction_col is not None:
+        if not isinstance(direction_col, str):
+            raise ValueError("direction_col must be the name of a df1 column")
+        names = _schema_names(df1)
+        if names is not None and direction_col not in names:
+            raise ValueError(f"direction_col '{direction_col}' not found in {names}")
+    _check_on_cols_present(on_cols, df1, df2)
+    zero_based = validate_coordinate_systems(df1, df2)
+    t1, t2, probe, build, n_contigs, _keys = _prepare(df1, df2, cols1, cols2, on_cols)
+    if direction_col is not None and direction_col not in t1.column_names:
+        raise ValueError(f"direction_col '{direction_col}' not found in {t1.column_names}")
+    is_minus = A.minus_rows(t1.column(direction_col)) if direction_col is not None else None
+    w_start, w_end = profile_windows(probe[1], probe[2], zero_based, anchor, upstream, downstream, is_minus)
+    bad = np.flatnonzero((w_start < -0x80000000) | (w_start > 0x7fffffff) | (w_end < -0x80000000) | (w_end > 0x7fffffff))
+    if bad.size:
+        r = int(bad[0])
+        raise ValueError(f"the window of df1 row {r} leaves the int32 range: [{int(w_start[r])}, {int(w_end[r])}] "
+                         f"(row {int(probe[1][r])} .. {int(probe[2][r])}, anchor={anchor!r}, upstream={upstream}, downstream={downstream})")
+    windows = (probe[0], w_start.astype(np.int32), w_end.astype(np.int32))
+    bases = default_engine().depth_profile(windows, is_minus, n_bins, build, strict=zero_based, n_contigs=n_contigs)
+    if output == "bases":
+        if output_type == "numpy.ndarray":
+            return bases
+        values = pa.array(bases.reshape(-1), type=pa.int64())
+    else:
+        lens = profile_bin_lengths(w_start, w_end, zero_based, n_bins, is_minus)
+        empty = lens <= 0
+        mean = np.divide(bases.astype(np.float64), lens.astype(np.float64), out=np.full(bases.shape, np.nan), where=~empty)
+        if output_type == "numpy.ndarray":
+            return mean
+        values = pa.array(mean.reshape(-1), type=pa.float64(), mask=empty.reshape(-1))
+    t = t1.append_column("profile", pa.FixedSizeListArray.from_arrays(values, n_bins))
+    return _finish_eager(t, output_type, zero_based, None)
 
 
 def _validate_thresholds(thresholds) -> list:
