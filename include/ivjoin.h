@@ -543,6 +543,48 @@ int ivj_overlap_agg_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, 
                         const ivj_thresholds* thr_dev /* NULL = plain predicate */, int64_t n_values, int32_t n_cols,
                         const ivj_agg_in* cols, const ivj_agg_out* agg_out);
 
+/* ---- signal_summary / signal_profile: build-side values weighted by the positions they share with the probe ------------------------
+ * The build (df2) side read as a signal track, (contig, start, end, value) rows as in a bedGraph: what bigWigAverageOverBed and
+ * deepTools computeMatrix compute.  For a probe row a and a build row b of one contig
+ *     ov(a, b) = min(a.end, b.end) - max(a.start, b.start)   (+ 1 for closed frames, Weak), in 64 bits
+ * and b CONTRIBUTES to a iff ov >= max(1, min_overlap, probe_min[a], build_min[b]) ("never" honoured) and its value is valid.
+ * thr == NULL leaves ov >= 1: rows of either side that cover no position share nothing, as in ivj_overlap_bases.  This is the
+ * thresholded predicate, NOT the plain one of ivj_overlap_agg with thr == NULL, which also counts rows that cover no position.
+ * Per value column of the build side, over the contributing rows (columns and outputs as ivj_agg_in / ivj_agg_out):
+ *   count  receives BASES = the sum of ov, accumulated as uint64 (modulo 2^64).  With a column without nulls and thr == NULL this
+ *          is ivj_overlap_bases; build rows that overlap each other count with their multiplicity.
+ *   sum    the sum of value * ov.  int64 columns: the product and the sum as uint64, i.e. the bits of a wrapping int64.  double
+ *          columns: value * (double)ov rounded once per row (ov <= 2^32 is exact), then added.  0 where bases == 0.
+ *   min / max   over the contributing VALUES, unweighted; doubles with fmin / fmax (NaN only where every value is NaN)
+ *   mean   (double)sum / (double)bases, the sum read as int64 for integer columns
+ * min, max and mean of a probe with bases == 0 are unspecified (the front door makes them nulls).  A NaN value makes sum and mean NaN.
+ * Values are indexed, results are placed, probes outside the dictionary are treated and a probe row_id is ignored as by
+ * ivj_overlap_agg.  Operations not asked for are not written.
+ * No pair is enumerated and there is no atomic: integer results are bit-identical from run to run; a double sum is evaluated in
+ * an order fixed by the sorted order of the index and the kernel's geometry (csrc/overlap_agg.hip.h, csrc/signal.hip.h) and
+ * repeats bit for bit for the same input rows in the same order on the same library build.
+ * Cost: one record, one predicate and one scan step per CANDIDATE of the probe's loose range, per value column.
+ * IVJ_EINVAL and IVJ_ESTATE as for ivj_overlap_agg.  (New entries change no existing struct or signature: IVJ_ABI_VERSION stays.) */
+int ivj_overlap_wagg(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts,
+                     const ivj_thresholds* thr /* NULL = ov >= 1 */, int32_t n_cols, const ivj_agg_in* cols /* over build rows */,
+                     const ivj_agg_out* agg_out /* caller-owned host columns of probe->n entries */);
+int ivj_overlap_wagg_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, const ivj_opts* opts,
+                         const ivj_thresholds* thr_dev /* NULL = ov >= 1 */, int64_t n_values, int32_t n_cols,
+                         const ivj_agg_in* cols, const ivj_agg_out* agg_out);
+/* The same statistics per BIN of every window row: the windows are cut as by ivj_depth_profile (x_j = S + floor(j L / n_bins),
+ * bin j = [x_j, x_{j+1}), 1 <= n_bins <= 4096, reverse as there) and every bin is a probe of ivj_overlap_wagg with thr == NULL, made
+ * on the device from the 12 bytes of its window: no bin frame exists in memory.  Every output column that was asked for is a
+ * row-major windows->n x n_bins matrix (caller buffer); an empty bin gets bases 0 and sum 0.  With a column of ones without nulls
+ * the bases matrix is ivj_depth_profile's; a row of the bases / sum matrices adds up to the window's ivj_overlap_wagg.
+ * opts->partition_mode is ignored: the windows are read in their own order.  There are no per-bin thresholds.
+ * Cost: as above per candidate of every BIN: a build row that spans k bins is visited k times, which suits tracks of short rows
+ * and not contig-wide rows.  IVJ_EINVAL: as ivj_overlap_wagg, and n_bins out of range; IVJ_ESTATE: an index without lookup tables. */
+int ivj_signal_profile(ivj_ctx* ctx, const ivj_side* windows, const uint8_t* reverse, int32_t n_bins, const ivj_side* build,
+                       const ivj_opts* opts, int32_t n_cols, const ivj_agg_in* cols /* over build rows */,
+                       const ivj_agg_out* agg_out /* caller-owned host matrices of windows->n * n_bins entries */);
+int ivj_signal_profile_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* windows_dev, const uint8_t* reverse_dev, int32_t n_bins,
+                           const ivj_opts* opts, int64_t n_values, int32_t n_cols, const ivj_agg_in* cols, const ivj_agg_out* agg_out);
+
 /* ---- permutation_test: overlap statistics of the probe side under circular shifts (regioneR circularRandomizeRegions) ---------------
  * Half-open coordinates: hs = start - (Weak ? 1 : 0), he = end; contig c covers [0, contig_len[c]), contig_len[c] >= 1.
  * offsets is an int32 table, row-major n_perm x opts->n_contigs, 0 <= offsets[p][c] < contig_len[c].

@@ -70,14 +70,20 @@ int overlap_agg_plan(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe, const i
     return IVJ_OK;
 }
 
-// One value column: gather -> reduce.  Device pointers; o.* hold P.n entries.  Enqueued on the context's stream.
-int overlap_agg_col(ivj_ctx* ctx, ivj_index* ix, const OaggPlan& P, const ivj_agg_in& in, int64_t n_values, const ivj_agg_out& o) {
-    if (P.n == 0) return IVJ_OK;
-    if (P.empty) return overlap_agg_zero(ctx, P.n, 1, &in, &o);
+// the value column and its validity bytes in index order (P.vals / P.ok)
+int overlap_agg_gather(ivj_ctx* ctx, ivj_index* ix, const OaggPlan& P, const ivj_agg_in& in, int64_t n_values) {
     if (n_values > 0)
         LAUNCH(ctx, "overlap_agg_gather", k_oagg_gather, grid1d(ix->n, 256), 256, (const int32_t*)ix->b_row, (const unsigned long long*)in.values,
                in.valid, ix->n, n_values, P.vals, P.ok);
     else HIP_TRY(hipMemsetAsync(P.ok, 0, (size_t)ix->n, ctx->stream));        // no values: every row is out of range
+    return IVJ_OK;
+}
+
+// One value column: gather -> reduce.  Device pointers; o.* hold P.n entries.  Enqueued on the context's stream.
+int overlap_agg_col(ivj_ctx* ctx, ivj_index* ix, const OaggPlan& P, const ivj_agg_in& in, int64_t n_values, const ivj_agg_out& o) {
+    if (P.n == 0) return IVJ_OK;
+    if (P.empty) return overlap_agg_zero(ctx, P.n, 1, &in, &o);
+    IVJ_TRY(overlap_agg_gather(ctx, ix, P, in, n_values));
     const int64_t grid = 8 * ((P.tiles + 7) / 8);
     IndexView v = view_of(ix);
     with_bool(P.strict, P.thresh, [&](auto S, auto T) {
@@ -101,6 +107,47 @@ int overlap_agg_check(const ivj_opts* opts, const ivj_side* probe, const ivj_thr
     IVJ_TRY(check_agg_cols(n_cols, cols, rows_present));
     if (!outs) return fail(IVJ_EINVAL, "agg_out is NULL");
     if (probe->n > 0) IVJ_TRY(check_agg_outs(n_cols, cols, outs));
+    return IVJ_OK;
+}
+
+// The host entries of the family: per value column the values (nb rows, + validity) go up, col(in, dev) enqueues the column's
+// passes on device pointers, and the result columns that were asked for (n entries each) come down -- through one staging block,
+// reused column after column.
+template <class ColFn>
+int agg_cols_host(ivj_ctx* ctx, int64_t n, int64_t nb, int32_t n_cols, const ivj_agg_in* cols, const ivj_agg_out* agg_out, ColFn&& col) {
+    const size_t col8 = align_up((size_t)n * 8), val8 = align_up((size_t)(nb + 1) * 8), val1 = align_up((size_t)nb + 1);
+    DevBuf stage;
+    hipError_t e = hipMalloc(&stage.p, val8 + val1 + 5 * col8);
+    if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(value and result columns): ") + hipGetErrorString(e));
+    char* base = (char*)stage.p;
+    void* d_val = base;
+    uint8_t* d_valid = (uint8_t*)(base + val8);
+    void* d_res[5];
+    for (int r = 0; r < 5; ++r) d_res[r] = base + val8 + val1 + (size_t)r * col8;
+    const ivj_agg_out dev{d_res[0], d_res[1], d_res[2], (double*)d_res[3], (int64_t*)d_res[4]};
+    int rc = IVJ_OK;
+    hipError_t ce = hipSuccess;
+    {
+        HostXfer copy(ctx->stream, &ctx->xfer);
+        for (int32_t k = 0; k < n_cols && rc == IVJ_OK; ++k) {
+            // the copies and the launches are ordered by the stream: column k + 1 overwrites the buffers after column k's copies left
+            const bool with_valid = nb > 0 && cols[k].valid;
+            if (nb > 0) copy.h2d(d_val, cols[k].values, (size_t)nb * 8);
+            if (with_valid) copy.h2d(d_valid, cols[k].valid, (size_t)nb);
+            const ivj_agg_in in{d_val, with_valid ? d_valid : nullptr, cols[k].dtype, cols[k].ops};
+            rc = col(in, dev);
+            const uint32_t ops = cols[k].ops;
+            const ivj_agg_out& o = agg_out[k];
+            if (ops & IVJ_AGG_SUM) copy.d2h(o.sum, dev.sum, (size_t)n * 8);
+            if (ops & IVJ_AGG_MIN) copy.d2h(o.min, dev.min, (size_t)n * 8);
+            if (ops & IVJ_AGG_MAX) copy.d2h(o.max, dev.max, (size_t)n * 8);
+            if (ops & IVJ_AGG_MEAN) copy.d2h(o.mean, dev.mean, (size_t)n * 8);
+            if (ops & IVJ_AGG_COUNT) copy.d2h(o.count, dev.count, (size_t)n * 8);
+        }
+        ce = copy.finish();
+    }
+    if (rc != IVJ_OK) return rc;
+    if (ce != hipSuccess) return fail(IVJ_EHIP, std::string("copies(overlap aggregates): ") + hipGetErrorString(ce));
     return IVJ_OK;
 }
 

@@ -39,6 +39,7 @@
 #include "select.hip.h"
 #include "merge_agg.hip.h"
 #include "overlap_agg.hip.h"
+#include "signal.hip.h"
 #include "permute.hip.h"
 
 using namespace ivj;
@@ -60,6 +61,7 @@ using namespace ivj;
 #include "host_thresh.hip.h"
 #include "host_select.hip.h"
 #include "host_overlap_agg.hip.h"
+#include "host_signal.hip.h"
 #include "host_permute.hip.h"
 #include "host_stream.hip.h"
 #include "host_comm.hip.h"
@@ -1508,41 +1510,62 @@ int ivj_overlap_agg(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, 
     ivj_index* ix = U.H.h.ix;
     OaggPlan P;
     IVJ_TRY(overlap_agg_plan(ctx, ix, &U.H.dp.s, opts, U.dthr, P));
-    // one value column with its validity bytes and the five result columns of one value column, reused column after column
-    const size_t col8 = align_up((size_t)n * 8), val8 = align_up((size_t)(nb + 1) * 8), val1 = align_up((size_t)nb + 1);
-    DevBuf stage;
-    hipError_t e = hipMalloc(&stage.p, val8 + val1 + 5 * col8);
-    if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(value and result columns): ") + hipGetErrorString(e));
-    char* base = (char*)stage.p;
-    void* d_val = base;
-    uint8_t* d_valid = (uint8_t*)(base + val8);
-    void* d_res[5];
-    for (int r = 0; r < 5; ++r) d_res[r] = base + val8 + val1 + (size_t)r * col8;
-    const ivj_agg_out dev{d_res[0], d_res[1], d_res[2], (double*)d_res[3], (int64_t*)d_res[4]};
-    int rc = IVJ_OK;
-    hipError_t ce = hipSuccess;
-    {
-        HostXfer copy(ctx->stream, &ctx->xfer);
-        for (int32_t k = 0; k < n_cols && rc == IVJ_OK; ++k) {
-            // the copies and the launches are ordered by the stream: column k + 1 overwrites the buffers after column k's copies left
-            const bool with_valid = nb > 0 && cols[k].valid;
-            if (nb > 0) copy.h2d(d_val, cols[k].values, (size_t)nb * 8);
-            if (with_valid) copy.h2d(d_valid, cols[k].valid, (size_t)nb);
-            const ivj_agg_in in{d_val, with_valid ? d_valid : nullptr, cols[k].dtype, cols[k].ops};
-            rc = overlap_agg_col(ctx, ix, P, in, nb, dev);
-            const uint32_t ops = cols[k].ops;
-            const ivj_agg_out& o = agg_out[k];
-            if (ops & IVJ_AGG_SUM) copy.d2h(o.sum, dev.sum, (size_t)n * 8);
-            if (ops & IVJ_AGG_MIN) copy.d2h(o.min, dev.min, (size_t)n * 8);
-            if (ops & IVJ_AGG_MAX) copy.d2h(o.max, dev.max, (size_t)n * 8);
-            if (ops & IVJ_AGG_MEAN) copy.d2h(o.mean, dev.mean, (size_t)n * 8);
-            if (ops & IVJ_AGG_COUNT) copy.d2h(o.count, dev.count, (size_t)n * 8);
-        }
-        ce = copy.finish();
-    }
-    if (rc != IVJ_OK) return rc;
-    if (ce != hipSuccess) return fail(IVJ_EHIP, std::string("copies(overlap aggregates): ") + hipGetErrorString(ce));
+    return agg_cols_host(ctx, n, nb, n_cols, cols, agg_out,
+                         [&](const ivj_agg_in& in, const ivj_agg_out& dev) { return overlap_agg_col(ctx, ix, P, in, nb, dev); });
+} IVJ_ABI_CATCH
+
+// ---------------------------------------------------------------- signal_summary / signal_profile: overlap-weighted build values (signal.hip.h)
+
+int ivj_overlap_wagg_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, const ivj_opts* opts, const ivj_thresholds* thr_dev,
+                         int64_t n_values, int32_t n_cols, const ivj_agg_in* cols, const ivj_agg_out* agg_out) try {
+    if (!ctx || !ix) return fail(IVJ_EINVAL, "ctx or index is NULL");
+    if (n_values < 0) return fail(IVJ_EINVAL, "n_values < 0");
+    IVJ_TRY(overlap_agg_check(opts, probe_dev, thr_dev, n_cols, cols, agg_out, ix->n > 0 && n_values > 0));
+    DeviceGuard g(ctx->device);
+    OaggPlan P;
+    IVJ_TRY(overlap_wagg_plan(ctx, ix, probe_dev, opts, thr_dev, P));
+    for (int32_t k = 0; k < n_cols; ++k) IVJ_TRY(overlap_wagg_col(ctx, ix, P, cols[k], n_values, agg_out[k]));
     return IVJ_OK;
+} IVJ_ABI_CATCH
+
+int ivj_overlap_wagg(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, const ivj_thresholds* thr,
+                     int32_t n_cols, const ivj_agg_in* cols, const ivj_agg_out* agg_out) try {
+    if (!ctx) return fail(IVJ_EINVAL, "ctx is NULL");
+    IVJ_TRY(check_side(build, "build"));
+    IVJ_TRY(overlap_agg_check(opts, probe, thr, n_cols, cols, agg_out, build->n > 0));
+    const int64_t n = probe->n, nb = build->n;
+    if (n == 0) return IVJ_OK;
+    DeviceGuard g(ctx->device);
+    SelectHost U;
+    IVJ_TRY(overlap_wagg_upload(ctx, probe, build, opts, thr, U));
+    ivj_index* ix = U.H.h.ix;
+    OaggPlan P;
+    IVJ_TRY(overlap_wagg_plan(ctx, ix, &U.H.dp.s, opts, U.dthr, P));
+    return agg_cols_host(ctx, n, nb, n_cols, cols, agg_out,
+                         [&](const ivj_agg_in& in, const ivj_agg_out& dev) { return overlap_wagg_col(ctx, ix, P, in, nb, dev); });
+} IVJ_ABI_CATCH
+
+int ivj_signal_profile_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* windows_dev, const uint8_t* reverse_dev, int32_t n_bins,
+                           const ivj_opts* opts, int64_t n_values, int32_t n_cols, const ivj_agg_in* cols, const ivj_agg_out* agg_out) try {
+    if (!ctx || !ix) return fail(IVJ_EINVAL, "ctx or index is NULL");
+    if (n_values < 0) return fail(IVJ_EINVAL, "n_values < 0");
+    IVJ_TRY(signal_profile_check(opts, windows_dev, n_bins, n_cols, cols, agg_out, ix->n > 0 && n_values > 0));
+    DeviceGuard g(ctx->device);
+    OaggPlan P;
+    IVJ_TRY(signal_profile_plan(ctx, ix, windows_dev, n_bins, opts, P));
+    for (int32_t k = 0; k < n_cols; ++k)
+        IVJ_TRY(signal_profile_col(ctx, ix, P, reverse_dev, windows_dev->n, n_bins, cols[k], n_values, agg_out[k]));
+    return IVJ_OK;
+} IVJ_ABI_CATCH
+
+int ivj_signal_profile(ivj_ctx* ctx, const ivj_side* windows, const uint8_t* reverse, int32_t n_bins, const ivj_side* build,
+                       const ivj_opts* opts, int32_t n_cols, const ivj_agg_in* cols, const ivj_agg_out* agg_out) try {
+    if (!ctx) return fail(IVJ_EINVAL, "ctx is NULL");
+    IVJ_TRY(check_side(build, "build"));
+    IVJ_TRY(signal_profile_check(opts, windows, n_bins, n_cols, cols, agg_out, build->n > 0));
+    if (windows->n == 0) return IVJ_OK;
+    DeviceGuard g(ctx->device);
+    return signal_profile_host(ctx, windows, reverse, n_bins, build, opts, n_cols, cols, agg_out);
 } IVJ_ABI_CATCH
 
 // ---------------------------------------------------------------- permutation_test: overlap statistics under circular shifts (permute.hip.h)

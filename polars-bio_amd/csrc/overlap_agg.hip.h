@@ -24,6 +24,11 @@
 // k_overlap_thresh; without, none but the rows flat_range itself rejects (outside the dictionary, empty contig) -- the plain
 // predicate is evaluated as written, so a row that covers no position counts what count_overlaps counts for it.
 // What bounds it: one record, one predicate and one scan step per CANDIDATE, not per match, and one sweep per value column.
+//
+// Two template arguments serve signal.hip.h (pb.signal_summary / pb.signal_profile) and leave the forms above as they were:
+// WEIGHTED makes a candidate contribute its value times the positions it shares with the probe (oagg_add_w) instead of its value
+// once, and the probe source Src (OaggRows here: the caller's probe columns) says where a tile's probes come from and where
+// their results go.
 #pragma once
 #include "thresh.hip.h"
 #include "merge_agg.hip.h"
@@ -52,6 +57,27 @@ __device__ __forceinline__ S oagg_bcast(const S& s, int src) {
     return o;
 }
 
+// positions a probe (qs, qe) shares with a build row (bs, be), as thresh_match computes them: <= 0 = none
+template <bool STRICT>
+__device__ __forceinline__ long long oagg_ov(int32_t qs, int32_t qe, int32_t bs, int32_t be) {
+    const long long lo = qs > bs ? qs : bs, hi = qe < be ? qe : be;
+    return hi - lo + (STRICT ? 0ll : 1ll);
+}
+
+// the weighted contribution of one candidate, 1 <= ov <= 2^32: cnt holds the shared positions (uint64 arithmetic, wrapping), sum
+// the value times ov -- int64 columns as a uint64 product, i.e. modulo 2^64; double columns as one correctly rounded product
+// ((double)ov is exact; __dmul_rn keeps it from being contracted into the additions that follow) -- min / max the bare value
+__device__ __forceinline__ void oagg_add_w(AggState<long long>& s, long long v, unsigned long long ov) {
+    s.cnt = (long long)((unsigned long long)s.cnt + ov);
+    s.sum += (unsigned long long)v * ov;
+    s.mn = v < s.mn ? v : s.mn; s.mx = v > s.mx ? v : s.mx;
+}
+__device__ __forceinline__ void oagg_add_w(AggState<double>& s, double v, unsigned long long ov) {
+    s.cnt = (long long)((unsigned long long)s.cnt + ov);
+    s.sum += __dmul_rn(v, (double)ov);
+    s.mn = fmin(s.mn, v); s.mx = fmax(s.mx, v);
+}
+
 template <class V> struct OaggLds {
     ThreshLds T;
     AggState<V> acc[THRESH_TILE];
@@ -61,7 +87,7 @@ template <class V> struct OaggLds {
 
 // One chunk of nC <= THRESH_CH candidates starting at tile-local candidate offset c0: the candidate -> probe map of thresh_chunk
 // (marks: probe index + 1 at the probe's first candidate of the chunk, max-scanned), then the walk described above.
-template <bool STRICT, bool THRESH, class V>
+template <bool STRICT, bool THRESH, bool WEIGHTED, class V>
 __device__ __forceinline__ void oagg_chunk(const IndexView& ix, const uint32_t* __restrict__ bm_sorted, const V* __restrict__ vals_sorted,
                                            const uint8_t* __restrict__ ok_sorted, long long c0, int nC, const long long (&off)[THRESH_ITEMS],
                                            const int (&cn)[THRESH_ITEMS], OaggLds<V>& L) {
@@ -127,9 +153,16 @@ __device__ __forceinline__ void oagg_chunk(const IndexView& ix, const uint32_t* 
             const int2 qq = L.T.q[q];
             const int p = lo + (int)(c0lo + (uint32_t)i - of);
             bool m = false;
+            unsigned long long ov = 0ull;                  // WEIGHTED: the positions shared with the probe
             if (valid) {
                 const int4 v = ix.rec4[p];                 // {start, end, build row, -}
-                if (THRESH) {
+                if (WEIGHTED) {                            // the thresholded predicate with its ov kept: contributes iff ov >= max(1, minima)
+                    uint32_t thr = L.T.thr[q];
+                    if (bm_sorted) { const uint32_t bm = bm_sorted[p]; thr = thr > bm ? thr : bm; }
+                    const long long o = oagg_ov<STRICT>(qq.x, qq.y, v.x, v.y);
+                    m = thr != THRESH_NEVER && o >= (thr > 1u ? (long long)thr : 1ll);
+                    ov = (unsigned long long)o;
+                } else if (THRESH) {
                     uint32_t thr = L.T.thr[q];
                     if (bm_sorted) { const uint32_t bm = bm_sorted[p]; thr = thr > bm ? thr : bm; }
                     m = thresh_match<STRICT>(qq.x, qq.y, v.x, v.y, thr);
@@ -140,7 +173,10 @@ __device__ __forceinline__ void oagg_chunk(const IndexView& ix, const uint32_t* 
             }
             if (__ballot(m) == 0ull && !carry_live) continue;  // uniform: every state of the step is the identity and nothing is carried
             S inc = S::identity();
-            if (m) inc.add(vals_sorted[p]);
+            if (m) {
+                if (WEIGHTED) oagg_add_w(inc, vals_sorted[p], ov);
+                else inc.add(vals_sorted[p]);
+            }
             // inclusive segmented scan: (a, b) -> (b.head ? b : a + b, a.head | b.head); a lane before the step's first start keeps
             // head == 0 and holds the fold from lane 0 on, which continues the carried segment
             int inc_head = starts ? 1 : 0;
@@ -178,32 +214,45 @@ __device__ __forceinline__ void oagg_chunk(const IndexView& ix, const uint32_t* 
     // (the barrier that opens the next chunk, or the one before the outputs are written, publishes acc)
 }
 
-// pos (NULL: identity) = the probe's position in the caller's columns when the probes were bucketed: probe_min is read and the
-// results are written there.  min_overlap / probe_min / bm_sorted are read by the THRESH form only.
-template <bool STRICT, bool THRESH, int DTYPE>
-__global__ __launch_bounds__(THRESH_THREADS, 3) void k_overlap_agg(IndexView ix, const int32_t* __restrict__ pc, const int32_t* __restrict__ ps,
-                                                                   const int32_t* __restrict__ pe, const int32_t* __restrict__ pos, int64_t n,
-                                                                   bool vec_ok, uint32_t min_overlap, const uint32_t* __restrict__ probe_min,
-                                                                   const uint32_t* __restrict__ bm_sorted,
-                                                                   const typename std::conditional<DTYPE == 0, long long, double>::type* __restrict__ vals_sorted,
-                                                                   const uint8_t* __restrict__ ok_sorted,
-                                                                   AggOut<typename std::conditional<DTYPE == 0, long long, double>::type> out) {
-    using V = typename std::conditional<DTYPE == 0, long long, double>::type;
+// Probe source of k_overlap_agg: the caller's probe columns.  pos (NULL: identity) = the probe's position in the caller's columns
+// when the probes were bucketed: probe_min is read and the results are written there.  A source hands a thread its THRESH_ITEMS
+// consecutive probes from i0 on as (contig, start, end) in the frame's own convention -- contig -1 for a probe that has none or
+// can match nothing -- and the output element of each.
+struct OaggRows {
+    using At = int32_t;
+    const int32_t *pc, *ps, *pe, *pos;
+    int64_t n;
+    bool vec_ok;
+    __device__ __forceinline__ int64_t count() const { return n; }
+    __device__ __forceinline__ void load(int64_t i0, int32_t (&c)[THRESH_ITEMS], int32_t (&s)[THRESH_ITEMS], int32_t (&e)[THRESH_ITEMS],
+                                         At (&at)[THRESH_ITEMS]) const {
+        load_items_nt(pc, i0, n, vec_ok, -1, c);
+        load_items_nt(ps, i0, n, vec_ok, 0, s);
+        load_items_nt(pe, i0, n, vec_ok, 0, e);
+        if (pos) load_items(pos, i0, n, vec_ok, 0, at);
+        else {
+#pragma unroll
+            for (int k = 0; k < THRESH_ITEMS; ++k) at[k] = (int32_t)(i0 + k);
+        }
+    }
+};
+
+// One tile of THRESH_TILE probes of `src`: ranges, the chunk walk, the outputs.  min_overlap / probe_min / bm_sorted are read by the
+// THRESH form only (WEIGHTED implies it: an effective minimum of 1).
+template <bool STRICT, bool THRESH, bool WEIGHTED, class V, class Src>
+__device__ __forceinline__ void oagg_tile(const IndexView& ix, const Src& src, uint32_t min_overlap, const uint32_t* __restrict__ probe_min,
+                                          const uint32_t* __restrict__ bm_sorted, const V* __restrict__ vals_sorted,
+                                          const uint8_t* __restrict__ ok_sorted, const AggOut<V>& out, OaggLds<V>& L) {
+    static_assert(THRESH || !WEIGHTED, "the weighted form is a thresholded form");
     using S = AggState<V>;
-    __shared__ OaggLds<V> L;
+    const int64_t n = src.count();
     const long long ntiles = (n + THRESH_TILE - 1) / THRESH_TILE;
     const long long tile = xcd_tile64(blockIdx.x, ntiles);
     if (tile >= ntiles) return;                            // uniform
     const int64_t i0 = (int64_t)tile * THRESH_TILE + (int64_t)threadIdx.x * THRESH_ITEMS;
-    int32_t c[THRESH_ITEMS], s[THRESH_ITEMS], e[THRESH_ITEMS], at[THRESH_ITEMS];
-    load_items_nt(pc, i0, n, vec_ok, -1, c);
-    load_items_nt(ps, i0, n, vec_ok, 0, s);
-    load_items_nt(pe, i0, n, vec_ok, 0, e);
-    if (pos) load_items(pos, i0, n, vec_ok, 0, at);
-    else {
-#pragma unroll
-        for (int k = 0; k < THRESH_ITEMS; ++k) at[k] = (int32_t)(i0 + k);
-    }
+    int32_t c[THRESH_ITEMS], s[THRESH_ITEMS], e[THRESH_ITEMS];
+    typename Src::At at[THRESH_ITEMS];
+    src.load(i0, c, s, e, at);
     int lo[THRESH_ITEMS], cn[THRESH_ITEMS];
     long long tsum = 0;
 #pragma unroll
@@ -228,12 +277,26 @@ __global__ __launch_bounds__(THRESH_THREADS, 3) void k_overlap_agg(IndexView ix,
     // (the first barrier inside oagg_chunk publishes the LDS arrays)
     for (long long c0 = 0; c0 < T; c0 += THRESH_CH) {
         const int nC = (int)((T - c0) < (long long)THRESH_CH ? (T - c0) : (long long)THRESH_CH);
-        oagg_chunk<STRICT, THRESH, V>(ix, bm_sorted, vals_sorted, ok_sorted, c0, nC, off, cn, L);
+        oagg_chunk<STRICT, THRESH, WEIGHTED, V>(ix, bm_sorted, vals_sorted, ok_sorted, c0, nC, off, cn, L);
     }
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < THRESH_ITEMS; ++k)
         if (i0 + k < n) magg_write(out, (int64_t)at[k], L.acc[threadIdx.x * THRESH_ITEMS + k]);
+}
+
+template <bool STRICT, bool THRESH, int DTYPE>
+__global__ __launch_bounds__(THRESH_THREADS, 3) void k_overlap_agg(IndexView ix, const int32_t* __restrict__ pc, const int32_t* __restrict__ ps,
+                                                                   const int32_t* __restrict__ pe, const int32_t* __restrict__ pos, int64_t n,
+                                                                   bool vec_ok, uint32_t min_overlap, const uint32_t* __restrict__ probe_min,
+                                                                   const uint32_t* __restrict__ bm_sorted,
+                                                                   const typename std::conditional<DTYPE == 0, long long, double>::type* __restrict__ vals_sorted,
+                                                                   const uint8_t* __restrict__ ok_sorted,
+                                                                   AggOut<typename std::conditional<DTYPE == 0, long long, double>::type> out) {
+    using V = typename std::conditional<DTYPE == 0, long long, double>::type;
+    __shared__ OaggLds<V> L;
+    const OaggRows src{pc, ps, pe, pos, n, vec_ok};
+    oagg_tile<STRICT, THRESH, false, V>(ix, src, min_overlap, probe_min, bm_sorted, vals_sorted, ok_sorted, out, L);
 }
 
 }  // namespace ivj

@@ -36,6 +36,7 @@ ABI_SYMBOLS = [
     "ivj_merge", "ivj_merged_free", "ivj_cluster", "ivj_coverage", "ivj_cluster_dev", "ivj_merge_dev", "ivj_coverage_dev",
     "ivj_merge_agg", "ivj_merge_agg_free", "ivj_merge_agg_dev",
     "ivj_overlap_agg", "ivj_overlap_agg_dev", "ivj_permute_overlaps", "ivj_permute_overlaps_dev",
+    "ivj_overlap_wagg", "ivj_overlap_wagg_dev", "ivj_signal_profile", "ivj_signal_profile_dev",
     "ivj_overlap_bases", "ivj_overlap_bases_dev", "ivj_depth_profile", "ivj_depth_profile_dev",
     "ivj_depth", "ivj_blocks_free", "ivj_depth_dev", "ivj_depth_summary", "ivj_depth_summary_dev",
     "ivj_setop", "ivj_regions_free", "ivj_set_stats", "ivj_setop_dev", "ivj_set_stats_dev",
@@ -271,6 +272,10 @@ def load_library() -> C.CDLL:
                                         C.POINTER(_AggOut), C.POINTER(C.c_int64)]
         L.ivj_overlap_agg.argtypes = [vp, P, P, O, T, C.c_int32, C.POINTER(_AggIn), C.POINTER(_AggOut)]
         L.ivj_overlap_agg_dev.argtypes = [vp, vp, P, O, T, C.c_int64, C.c_int32, C.POINTER(_AggIn), C.POINTER(_AggOut)]
+        L.ivj_overlap_wagg.argtypes = L.ivj_overlap_agg.argtypes
+        L.ivj_overlap_wagg_dev.argtypes = L.ivj_overlap_agg_dev.argtypes
+        L.ivj_signal_profile.argtypes = [vp, P, vp, C.c_int32, P, O, C.c_int32, C.POINTER(_AggIn), C.POINTER(_AggOut)]
+        L.ivj_signal_profile_dev.argtypes = [vp, vp, P, vp, C.c_int32, O, C.c_int64, C.c_int32, C.POINTER(_AggIn), C.POINTER(_AggOut)]
         L.ivj_permute_overlaps.argtypes = [vp, P, P, O, vp, vp, C.c_int64, vp, vp]
         L.ivj_permute_overlaps_dev.argtypes = [vp, vp, P, O, vp, vp, C.c_int64, vp, vp]
         L.ivj_depth.argtypes = [vp, P, O, C.POINTER(_Blocks)]
@@ -1028,6 +1033,25 @@ class Engine:
         t, keep = self._host_thresholds(ps, bs, min_overlap, probe_min, build_min)
         return C.byref(t), (t, keep)
 
+    def _agg_columns(self, agg, n_build: int, shape):
+        """The ivj_agg_in / ivj_agg_out arrays of a host call: ``agg`` = a list of (values, valid, ops) per value column of the build
+        side; every result array has ``shape``.  -> (n_cols, cols, outs, results, keep-alive)."""
+        agg = list(agg)
+        cols = (_AggIn * max(len(agg), 1))()
+        outs = (_AggOut * max(len(agg), 1))()
+        keep, results = [], []
+        size = int(np.prod(shape))
+        for k, (values, valid, ops) in enumerate(agg):
+            values, valid, ops = _agg_column(values, valid, ops, n_build)
+            keep.append((values, valid))
+            cols[k] = _AggIn(values.ctypes.data if n_build else None, valid.ctypes.data if valid is not None and n_build else None,
+                             AGG_I64 if values.dtype == np.int64 else AGG_F64, ops)
+            kinds = {"sum": values.dtype, "min": values.dtype, "max": values.dtype, "mean": np.float64, "count": np.int64}
+            res = {name: np.zeros(shape, kinds[name]) for name, bit in AGG_OPS.items() if ops & bit}
+            outs[k] = _AggOut(*(res[name].ctypes.data if name in res and size else None for name in ("sum", "min", "max", "mean", "count")))
+            results.append(res)
+        return len(agg), cols, outs, results, keep
+
     def overlap_agg(self, probe, build, strict: bool, n_contigs: int, agg, min_overlap: int = 0, probe_min=None, build_min=None,
                     partition_mode: int = 0):
         """pb.map_overlaps (ivj_overlap_agg): ``agg`` = a list of (values, valid, ops) per value column of the BUILD side, as in
@@ -1035,25 +1059,43 @@ class Engine:
         thresholded one when min_overlap / probe_min / build_min are given -> [dict per column] mapping each requested name to an
         array of one entry per probe row, probe order kept: sum int64 (wrapped) / float64, min / max the column's type, mean
         float64, count int64.  sum and count are 0 where nothing valid matches; min / max / mean are unspecified there."""
+        return self._overlap_agg_call("ivj_overlap_agg", probe, build, strict, n_contigs, agg, min_overlap, probe_min, build_min, partition_mode)
+
+    def overlap_wagg(self, probe, build, strict: bool, n_contigs: int, agg, min_overlap: int = 0, probe_min=None, build_min=None,
+                     partition_mode: int = 0):
+        """pb.signal_summary (ivj_overlap_wagg): as ``overlap_agg``, but a build row contributes iff it shares ov >= max(1, minima)
+        positions with the probe row, and then weighs ov: ``count`` receives the bases (sum of ov), ``sum`` the sum of value * ov
+        (int64 wrapped / float64), ``mean`` = sum / bases; ``min`` / ``max`` are over the contributing values, unweighted."""
+        return self._overlap_agg_call("ivj_overlap_wagg", probe, build, strict, n_contigs, agg, min_overlap, probe_min, build_min, partition_mode)
+
+    def _overlap_agg_call(self, entry, probe, build, strict, n_contigs, agg, min_overlap, probe_min, build_min, partition_mode):
         ps, keep_p = _host_side(*probe)
         bs, keep_b = _host_side(*build)
         t, keep_t = self._optional_thresholds(ps, bs, min_overlap, probe_min, build_min)
         o = make_opts(strict, n_contigs, partition_mode=partition_mode)
-        agg = list(agg)
-        cols = (_AggIn * max(len(agg), 1))()
-        outs = (_AggOut * max(len(agg), 1))()
-        keep, results = [], []
-        for k, (values, valid, ops) in enumerate(agg):
-            values, valid, ops = _agg_column(values, valid, ops, bs.n)
-            keep.append((values, valid))
-            cols[k] = _AggIn(values.ctypes.data if bs.n else None, valid.ctypes.data if valid is not None and bs.n else None,
-                             AGG_I64 if values.dtype == np.int64 else AGG_F64, ops)
-            kinds = {"sum": values.dtype, "min": values.dtype, "max": values.dtype, "mean": np.float64, "count": np.int64}
-            res = {name: np.zeros(ps.n, kinds[name]) for name, bit in AGG_OPS.items() if ops & bit}
-            outs[k] = _AggOut(*(res[name].ctypes.data if name in res and ps.n else None for name in ("sum", "min", "max", "mean", "count")))
-            results.append(res)
-        _check(self.L, self.L.ivj_overlap_agg(self.h, C.byref(ps), C.byref(bs), C.byref(o), t, len(agg), cols, outs), "ivj_overlap_agg")
+        k, cols, outs, results, keep = self._agg_columns(agg, bs.n, (ps.n,))
+        _check(self.L, getattr(self.L, entry)(self.h, C.byref(ps), C.byref(bs), C.byref(o), t, k, cols, outs), entry)
         del keep_p, keep_b, keep_t, keep
+        return results
+
+    def signal_profile(self, windows, reverse, n_bins: int, build, strict: bool, n_contigs: int, agg):
+        """pb.signal_profile (ivj_signal_profile): every window row cut into n_bins bins as by ``depth_profile``, every bin a probe of
+        ``overlap_wagg`` without thresholds -> [dict per column] of (n, n_bins) arrays, window order; ``reverse``: None or one flag
+        per window, a flagged row comes back right to left."""
+        ws, keep_w = _host_side(*windows)
+        bs, keep_b = _host_side(*build)
+        o = make_opts(strict, n_contigs)
+        rev = None
+        if reverse is not None:
+            rev = np.ascontiguousarray(np.asarray(reverse).astype(bool).astype(np.uint8))
+            if rev.shape != (ws.n,):
+                raise ValueError(f"reverse must hold one flag per window ({ws.n}), got shape {rev.shape}")
+        n_bins = int(n_bins)
+        # a bin count the entry refuses gets no matrix: the entry checks n_bins before it looks at the outputs
+        k, cols, outs, results, keep = self._agg_columns(agg, bs.n, (ws.n, n_bins if 1 <= n_bins <= DEPTH_PROFILE_MAX_BINS else 0))
+        _check(self.L, self.L.ivj_signal_profile(self.h, C.byref(ws), rev.ctypes.data if rev is not None and ws.n else None, n_bins,
+                                                  C.byref(bs), C.byref(o), k, cols, outs), "ivj_signal_profile")
+        del keep_w, keep_b, keep
         return results
 
     def overlap_select(self, probe, build, strict: bool, n_contigs: int, mode, min_overlap: int = 0, probe_min=None, build_min=None,
@@ -1291,6 +1333,29 @@ class Engine:
             cout[i] = _AggOut(*(outs[i].get(name) or None for name in ("sum", "min", "max", "mean", "count")))
         _check(self.L, self.L.ivj_overlap_agg_dev(self.h, ix.handle, C.byref(probe), C.byref(opts), C.byref(thr) if thr is not None else None,
                                                   int(n_values), k, cin, cout), "ivj_overlap_agg_dev")
+
+    def overlap_wagg_dev(self, ix: DeviceIndex, probe: _Side, opts: _Opts, thr: Optional[_Thresholds], n_values: int, cols, outs):
+        """ivj_overlap_wagg_dev; ``thr`` None = every row that shares a position.  Arguments as ``overlap_agg_dev``; the ``count``
+        column receives the bases."""
+        k = len(cols)
+        cin = (_AggIn * max(k, 1))()
+        cout = (_AggOut * max(k, 1))()
+        for i, (values_ptr, valid_ptr, dtype, ops) in enumerate(cols):
+            cin[i] = _AggIn(values_ptr or None, valid_ptr or None, int(dtype), int(ops))
+            cout[i] = _AggOut(*(outs[i].get(name) or None for name in ("sum", "min", "max", "mean", "count")))
+        _check(self.L, self.L.ivj_overlap_wagg_dev(self.h, ix.handle, C.byref(probe), C.byref(opts), C.byref(thr) if thr is not None else None,
+                                                   int(n_values), k, cin, cout), "ivj_overlap_wagg_dev")
+
+    def signal_profile_dev(self, ix: DeviceIndex, windows: _Side, reverse_ptr: int, n_bins: int, opts: _Opts, n_values: int, cols, outs):
+        """ivj_signal_profile_dev.  ``cols`` / ``outs`` as in ``overlap_wagg_dev``, every output a row-major windows.n x n_bins matrix."""
+        k = len(cols)
+        cin = (_AggIn * max(k, 1))()
+        cout = (_AggOut * max(k, 1))()
+        for i, (values_ptr, valid_ptr, dtype, ops) in enumerate(cols):
+            cin[i] = _AggIn(values_ptr or None, valid_ptr or None, int(dtype), int(ops))
+            cout[i] = _AggOut(*(outs[i].get(name) or None for name in ("sum", "min", "max", "mean", "count")))
+        _check(self.L, self.L.ivj_signal_profile_dev(self.h, ix.handle, C.byref(windows), C.c_void_p(reverse_ptr or None), int(n_bins),
+                                                     C.byref(opts), int(n_values), k, cin, cout), "ivj_signal_profile_dev")
 
     def depth_dev(self, ix: DeviceIndex, opts: _Opts, capacity: int, contig_ptr: int, start_ptr: int, end_ptr: int, depth_ptr: int):
         """-> (n_blocks, fits).  fits=False: nothing was written, grow the buffers to n_blocks."""

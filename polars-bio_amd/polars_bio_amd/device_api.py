@@ -267,11 +267,19 @@ class DeviceJoin:
         thresholded one when min_overlap / probe_min / build_min are given (as in ``count_overlaps_thresh``).  -> one dict per
         column, name -> tensor of probe.n elements in probe order: sum int64 (wrapped) / float64, min / max the column's type,
         mean float64, count int64.  sum and count are 0 where nothing valid matches; min / max / mean are unspecified there."""
+        return self._overlap_agg(False, probe, build, strict, n_contigs, agg, min_overlap, probe_min, build_min, index, partition_mode)
+
+    def overlap_wagg(self, probe: DeviceSide, build: DeviceSide, strict: bool, n_contigs: int, agg, min_overlap: int = 0, probe_min=None,
+                     build_min=None, index=None, partition_mode: int = 0):
+        """The build side as a signal track (ivj_overlap_wagg_dev), all in HBM: arguments and results as ``overlap_agg``, but a build
+        row contributes iff it shares ov >= max(1, minima) positions with the probe row and then weighs ov -- ``count`` holds the
+        bases (sum of ov), ``sum`` the sum of value * ov (int64 wrapped / float64), ``mean`` = sum / bases, ``min`` / ``max`` the
+        extremes of the contributing values, unweighted.  Rows of either side that cover no position share nothing."""
+        return self._overlap_agg(True, probe, build, strict, n_contigs, agg, min_overlap, probe_min, build_min, index, partition_mode)
+
+    def _agg_columns(self, agg):
+        """-> ([(values, valid, dtype, ops mask)], n_values) of a list of (values, valid, ops) on CUDA tensors."""
         torch = self.torch
-        opts = make_opts(strict, n_contigs, partition_mode=partition_mode)
-        dev = probe.start.device
-        plain = not min_overlap and probe_min is None and build_min is None
-        thr = None if plain else self._thresholds(probe, build, min_overlap, probe_min, build_min)
         cols = []
         for values, valid, ops in list(agg):
             if values.dtype not in (torch.int64, torch.float64) or not values.is_cuda or not values.is_contiguous() or values.dim() != 1:
@@ -283,19 +291,59 @@ class DeviceJoin:
         lengths = {int(v.shape[0]) for v, _, _, _ in cols}
         if len(lengths) > 1:
             raise ValueError(f"the value columns of one call must have one length, got {sorted(lengths)}")
-        n_values = lengths.pop() if lengths else 0
+        return cols, (lengths.pop() if lengths else 0)
+
+    def _agg_results(self, cols, shape, dev):
+        torch = self.torch
         kinds = {"sum": None, "min": None, "max": None, "mean": torch.float64, "count": torch.int64}
-        results = [{name: torch.zeros(probe.n, dtype=kinds[name] or values.dtype, device=dev) for name, bit in AGG_OPS.items() if ops & bit}
-                   for values, _, _, ops in cols]
+        return [{name: torch.zeros(shape, dtype=kinds[name] or values.dtype, device=dev) for name, bit in AGG_OPS.items() if ops & bit}
+                for values, _, _, ops in cols]
+
+    def _overlap_agg(self, weighted, probe, build, strict, n_contigs, agg, min_overlap, probe_min, build_min, index, partition_mode):
+        opts = make_opts(strict, n_contigs, partition_mode=partition_mode)
+        plain = not min_overlap and probe_min is None and build_min is None
+        thr = None if plain else self._thresholds(probe, build, min_overlap, probe_min, build_min)
+        cols, n_values = self._agg_columns(agg)
+        results = self._agg_results(cols, probe.n, probe.start.device)
         if build.n == 0:
             plain, thr = True, None                            # every count is 0 under either predicate
         own = index is None
-        ix = self.engine.index_build_dev(build.as_c(), opts, plain) if own else index
+        # (the weighted walk is the thresholded one: it reads no end order)
+        ix = self.engine.index_build_dev(build.as_c(), opts, plain and not weighted) if own else index
         try:
-            self.engine.overlap_agg_dev(
+            (self.engine.overlap_wagg_dev if weighted else self.engine.overlap_agg_dev)(
                 ix, probe.as_c(), opts, thr, n_values,
                 [(v.data_ptr() if n_values else 0, (m.data_ptr() if m is not None and n_values else 0), dt, ops) for v, m, dt, ops in cols],
                 [{name: (t.data_ptr() if probe.n else 0) for name, t in r.items()} for r in results])
+        finally:
+            if own:
+                ix.close()
+        return results
+
+    def signal_profile(self, windows: DeviceSide, build: DeviceSide, strict: bool, n_contigs: int, n_bins: int, agg, reverse=None,
+                       index=None):
+        """Every window row cut into ``n_bins`` bins as by ``depth_profile``, every bin a probe of ``overlap_wagg`` without
+        thresholds (ivj_signal_profile_dev) -> one dict per column of ``agg``, name -> tensor (windows.n, n_bins) in HBM.
+        ``reverse``: None or a bool / uint8 CUDA tensor of windows.n flags, a flagged row comes back right to left."""
+        torch = self.torch
+        n_bins = int(n_bins)
+        opts = make_opts(strict, n_contigs)
+        dev = windows.start.device
+        rev = None
+        if reverse is not None:
+            rev = reverse.to(torch.uint8) if reverse.dtype == torch.bool else reverse
+            if rev.dtype != torch.uint8 or tuple(rev.shape) != (windows.n,) or not rev.is_contiguous() or rev.device != dev:
+                raise ValueError("reverse must be a contiguous bool / uint8 tensor of windows.n elements on the windows' device")
+        cols, n_values = self._agg_columns(agg)
+        results = self._agg_results(cols, (windows.n, max(n_bins, 0)), dev)
+        own = index is None
+        ix = self.engine.index_build_dev(build.as_c(), opts, False) if own else index
+        try:
+            # (a tensor without elements has no address: the entry still checks n_bins, and refuses a NULL output only with rows)
+            self.engine.signal_profile_dev(
+                ix, windows.as_c(), rev.data_ptr() if rev is not None and windows.n else 0, n_bins, opts, n_values,
+                [(v.data_ptr() if n_values else 0, (m.data_ptr() if m is not None and n_values else 0), dt, ops) for v, m, dt, ops in cols],
+                [{name: (t.data_ptr() if t.numel() else 0) for name, t in r.items()} for r in results])
         finally:
             if own:
                 ix.close()

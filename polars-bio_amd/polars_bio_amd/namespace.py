@@ -16,6 +16,7 @@ _ALIASES = {
     "coverage": (range_op.coverage, True), "mean_depth": (range_op.mean_depth, True), "depth_summary": (range_op.depth_summary, True),
     "depth_profile": (range_op.depth_profile, True),
     "subtract": (range_op.subtract, True), "map_overlaps": (range_op.map_overlaps, True),
+    "signal_summary": (range_op.signal_summary, True), "signal_profile": (range_op.signal_profile, True),
     "permutation_test": (range_op.permutation_test, True),
     "merge": (range_op.merge, False), "depth": (range_op.depth, False), "cluster": (range_op.cluster, False), "complement": (range_op.complement, False),
     "set_intersect": (range_op.set_intersect, True), "set_union": (range_op.set_union, True), "set_difference": (range_op.set_difference, True),

@@ -27,7 +27,7 @@ from .constants import DEFAULT_INTERVAL_COLUMNS
 
 logger = logging.getLogger("polars_bio_amd")
 
-__all__ = ["overlap", "overlap_batches", "count_overlaps_batches", "nearest_batches", "nearest", "count_overlaps", "coverage", "mean_depth", "depth_profile", "depth_summary", "merge", "cluster", "complement", "subtract", "map_overlaps",
+__all__ = ["overlap", "overlap_batches", "count_overlaps_batches", "nearest_batches", "nearest", "count_overlaps", "coverage", "mean_depth", "depth_profile", "depth_summary", "merge", "cluster", "complement", "subtract", "map_overlaps", "signal_summary", "signal_profile",
            "set_intersect", "set_union", "set_difference", "set_symmetric_difference", "jaccard", "multi_intersect", "consensus",
            "FilterOp", "RangeOp", "OverlapOutputMode"]
 
@@ -867,6 +867,48 @@ def profile_bin_lengths(w_start, w_end, zero_based: bool, n_bins: int, reverse=N
     return lens
 
 
+def _profile_setup(df1, df2, n_bins, anchor, upstream, downstream, direction_col, on_cols, cols1, cols2, output, outputs, output_type):
+    """What ``depth_profile`` and ``signal_profile`` share: the argument checks in the order their messages have always come, the
+    encoded frames and the int32 window of every df1 row.
+    -> (n_bins, zero_based, t1, t2, build, n_contigs, on_cols, is_minus, w_start, w_end, windows)."""
+    on_cols = _validate_overlap_input(cols1, cols2, on_cols, ("_1", "_2"), "pyarrow.Table" if output_type == "numpy.ndarray" else output_type)
+    if isinstance(n_bins, (bool, np.bool_)) or not isinstance(n_bins, (int, np.integer)) or not 1 <= int(n_bins) <= DEPTH_PROFILE_MAX_BINS:
+        raise ValueError(f"n_bins must be an int in 1 .. {DEPTH_PROFILE_MAX_BINS}, got {n_bins!r}")
+    n_bins = int(n_bins)
+    if output not in outputs:
+        raise ValueError(f"output must be {' or '.join(repr(o) for o in outputs) if len(outputs) == 2 else 'one of ' + str(outputs)}, got {output!r}")
+    if anchor is not None and anchor not in _PROFILE_ANCHORS:
+        raise ValueError(f"anchor must be None or one of {_PROFILE_ANCHORS}, got {anchor!r}")
+    for name, v in (("upstream", upstream), ("downstream", downstream)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= 0xffffffff:
+            raise ValueError(f"{name} must be an int in 0 .. 2^32 - 1, got {v!r}")
+    upstream, downstream = int(upstream), int(downstream)
+    if anchor is None and (upstream or downstream):
+        raise ValueError(f"upstream / downstream need an anchor ('start', 'end' or 'center'), got upstream={upstream}, downstream={downstream} with anchor=None")
+    if anchor is not None and upstream + downstream < 1:
+        raise ValueError(f"anchor={anchor!r} needs upstream + downstream >= 1, got {upstream} + {downstream}")
+    if direction_col is not None:
+        if not isinstance(direction_col, str):
+            raise ValueError("direction_col must be the name of a df1 column")
+        names = _schema_names(df1)
+        if names is not None and direction_col not in names:
+            raise ValueError(f"direction_col '{direction_col}' not found in {names}")
+    _check_on_cols_present(on_cols, df1, df2)
+    zero_based = validate_coordinate_systems(df1, df2)
+    t1, t2, probe, build, n_contigs, _keys = _prepare(df1, df2, cols1, cols2, on_cols)
+    if direction_col is not None and direction_col not in t1.column_names:
+        raise ValueError(f"direction_col '{direction_col}' not found in {t1.column_names}")
+    is_minus = A.minus_rows(t1.column(direction_col)) if direction_col is not None else None
+    w_start, w_end = profile_windows(probe[1], probe[2], zero_based, anchor, upstream, downstream, is_minus)
+    bad = np.flatnonzero((w_start < -0x80000000) | (w_start > 0x7fffffff) | (w_end < -0x80000000) | (w_end > 0x7fffffff))
+    if bad.size:
+        r = int(bad[0])
+        raise ValueError(f"the window of df1 row {r} leaves the int32 range: [{int(w_start[r])}, {int(w_end[r])}] "
+                         f"(row {int(probe[1][r])} .. {int(probe[2][r])}, anchor={anchor!r}, upstream={upstream}, downstream={downstream})")
+    windows = (probe[0], w_start.astype(np.int32), w_end.astype(np.int32))
+    return n_bins, zero_based, t1, t2, build, n_contigs, on_cols, is_minus, w_start, w_end, windows
+
+
 def depth_profile(
     df1,
     df2,
@@ -905,43 +947,10 @@ def depth_profile(
     half-open, 1-based frames closed.  Rows of df2 that cover no position and rows with a null chrom share nothing.
     ``on_cols``: only df2 intervals of the df1 row's group of equal (chrom, on values) count; a null on-value matches nothing.
 
-    Eager.  Not covered: a value / weight column on df2 (bedGraph signal), streaming inputs or outputs, several devices, per-bin
-    statistics other than the sum / mean."""
-    on_cols = _validate_overlap_input(cols1, cols2, on_cols, ("_1", "_2"), "pyarrow.Table" if output_type == "numpy.ndarray" else output_type)
-    if isinstance(n_bins, (bool, np.bool_)) or not isinstance(n_bins, (int, np.integer)) or not 1 <= int(n_bins) <= DEPTH_PROFILE_MAX_BINS:
-        raise ValueError(f"n_bins must be an int in 1 .. {DEPTH_PROFILE_MAX_BINS}, got {n_bins!r}")
-    n_bins = int(n_bins)
-    if output not in ("mean", "bases"):
-        raise ValueError(f"output must be 'mean' or 'bases', got {output!r}")
-    if anchor is not None and anchor not in _PROFILE_ANCHORS:
-        raise ValueError(f"anchor must be None or one of {_PROFILE_ANCHORS}, got {anchor!r}")
-    for name, v in (("upstream", upstream), ("downstream", downstream)):
-        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= 0xffffffff:
-            raise ValueError(f"{name} must be an int in 0 .. 2^32 - 1, got {v!r}")
-    upstream, downstream = int(upstream), int(downstream)
-    if anchor is None and (upstream or downstream):
-        raise ValueError(f"upstream / downstream need an anchor ('start', 'end' or 'center'), got upstream={upstream}, downstream={downstream} with anchor=None")
-    if anchor is not None and upstream + downstream < 1:
-        raise ValueError(f"anchor={anchor!r} needs upstream + downstream >= 1, got {upstream} + {downstream}")
-    if direction_col is not None:
-        if not isinstance(direction_col, str):
-            raise ValueError("direction_col must be the name of a df1 column")
-        names = _schema_names(df1)
-        if names is not None and direction_col not in names:
-            raise ValueError(f"direction_col '{direction_col}' not found in {names}")
-    _check_on_cols_present(on_cols, df1, df2)
-    zero_based = validate_coordinate_systems(df1, df2)
-    t1, t2, probe, build, n_contigs, _keys = _prepare(df1, df2, cols1, cols2, on_cols)
-    if direction_col is not None and direction_col not in t1.column_names:
-        raise ValueError(f"direction_col '{direction_col}' not found in {t1.column_names}")
-    is_minus = A.minus_rows(t1.column(direction_col)) if direction_col is not None else None
-    w_start, w_end = profile_windows(probe[1], probe[2], zero_based, anchor, upstream, downstream, is_minus)
-    bad = np.flatnonzero((w_start < -0x80000000) | (w_start > 0x7fffffff) | (w_end < -0x80000000) | (w_end > 0x7fffffff))
-    if bad.size:
-        r = int(bad[0])
-        raise ValueError(f"the window of df1 row {r} leaves the int32 range: [{int(w_start[r])}, {int(w_end[r])}] "
-                         f"(row {int(probe[1][r])} .. {int(probe[2][r])}, anchor={anchor!r}, upstream={upstream}, downstream={downstream})")
-    windows = (probe[0], w_start.astype(np.int32), w_end.astype(np.int32))
+    Eager.  A value / weight column on df2 (bedGraph signal) is ``signal_profile``'s.  Not covered: streaming inputs or outputs,
+    several devices, per-bin statistics other than the sum / mean."""
+    n_bins, zero_based, t1, t2, build, n_contigs, on_cols, is_minus, w_start, w_end, windows = _profile_setup(
+        df1, df2, n_bins, anchor, upstream, downstream, direction_col, on_cols, cols1, cols2, output, ("mean", "bases"), output_type)
     bases = default_engine().depth_profile(windows, is_minus, n_bins, build, strict=zero_based, n_contigs=n_contigs)
     if output == "bases":
         if output_type == "numpy.ndarray":
@@ -1148,10 +1157,10 @@ def merge(
     return A.from_arrow(pa.table(data), output_type, zero_based)
 
 
-def _map_engine():
+def _map_engine(what: str = "map_overlaps", entry: str = "overlap_agg"):
     eng = default_engine()
-    if not hasattr(eng, "overlap_agg"):
-        raise NotImplementedError(f"map_overlaps needs a single-device engine; the default engine is a {type(eng).__name__} "
+    if not hasattr(eng, entry):
+        raise NotImplementedError(f"{what} needs a single-device engine; the default engine is a {type(eng).__name__} "
                                   "(several devices), which has no overlap aggregates")
     return eng
 
@@ -1212,6 +1221,172 @@ def map_overlaps(
         for out, column in _agg_outputs(name, ops, t2.schema.field(name).type, res).items():
             table = table.append_column(out, column)
     return _finish_eager(table, output_type, zero_based, limit)
+
+
+_SIGNAL_STATS = ("size", "bases", "sum", "mean0", "mean", "min", "max")
+_SIGNAL_PROFILE_OUTPUTS = ("mean", "mean0", "sum", "bases", "min", "max")
+
+
+def _signal_values(value, t2: pa.Table, cols2, on_cols, single_only: bool):
+    """``value`` -> (names, single): a df2 column name, or (``signal_summary``) a non-empty list of distinct names; the columns
+    are checked as ``map_overlaps`` checks its ``agg`` columns."""
+    single = isinstance(value, str)
+    if single_only and not single:
+        raise ValueError(f"value must be the name of one df2 column, got {value!r}")
+    names = [value] if single else list(value) if isinstance(value, (list, tuple)) else None
+    if not names or not all(isinstance(n, str) for n in names):
+        raise ValueError(f"value must be the name of a df2 column or a non-empty list of names, got {value!r}")
+    if len(set(names)) != len(names):
+        raise ValueError(f"value names a column twice: {names}")
+    _validate_agg({name: "sum" for name in names}, t2, cols2, on_cols)
+    return names, single
+
+
+def signal_summary(
+    df1,
+    df2,
+    value,
+    on_cols: Union[list, None] = None,
+    cols1: Union[list, None] = ["chrom", "start", "end"],
+    cols2: Union[list, None] = ["chrom", "start", "end"],
+    output_type: str = "polars.LazyFrame",
+    limit: Union[int, None] = None,
+    *,
+    min_overlap: Union[int, None] = None,
+    min_frac1: Union[float, None] = None,
+    min_frac2: Union[float, None] = None,
+):
+    """Summarise a signal track over every df1 interval: df2 holds (chrom, start, end, ``value``) rows as a bedGraph does, and a
+    df2 row weighs its value on every position it shares with the df1 row -- ``bigWigAverageOverBed`` (with ``-minMax``),
+    ``multiBigwigSummary BED-file``, ``bedtools map`` on a bedGraph done right.  Reduced on the device: no pair is enumerated.
+
+    With ov = the positions a df2 row shares with the df1 row (0-based frames half-open, 1-based closed), a df2 row contributes
+    iff ov >= 1 and its value is not null -- rows of either side that cover no position share nothing, as in ``mean_depth``;
+    this is NOT what the unthresholded ``map_overlaps`` counts.  Output: df1's columns, one row per df1 row in df1 order, plus
+
+      ``size``   Int64, the positions of the df1 row (0 if it has none)
+      ``bases``  Int64, the sum of ov over the contributing df2 rows.  df2 rows that overlap each other count with their
+                 multiplicity: ``bases`` can exceed ``size`` then (a proper bedGraph has no such rows, and there it is ``covered``)
+      ``sum``    the sum of value * ov: Int64 for integer columns, wrapping modulo 2^64; Float64 for float columns
+      ``mean0``  Float64 sum / size, null where size is 0 (positions without signal count as 0)
+      ``mean``   Float64 sum / bases, null where bases is 0 (positions without signal are left out)
+      ``min`` / ``max``  the column's own type, over the contributing values (unweighted), null where bases is 0
+
+    ``value`` is a df2 column name, or a list of names: with a list every output is suffixed ``_<name>`` (``size_score``,
+    ``sum_score``, ...), a single string gives the bare names.  Columns may be signed integers, unsigned integers up to 32
+    bits, float32 or float64, not the interval or ``on_cols`` columns.  A NaN value makes ``sum`` / ``mean0`` / ``mean`` of its
+    df1 row NaN; ``min`` / ``max`` skip NaNs unless every value is NaN.  Integer results are identical from run to run; a float
+    ``sum`` is evaluated in a fixed order and repeats bit for bit for the same rows in the same order.  An output name that is
+    already a df1 column is a ValueError.
+
+    ``on_cols`` and ``min_overlap`` / ``min_frac1`` / ``min_frac2`` (keyword-only) as in ``map_overlaps``: only df2 rows of the
+    df1 row's group, and only those that pass the overlap thresholds, contribute.  The cost is one test per candidate df2 row of
+    each df1 row and value column.
+
+    Eager whatever the ``output_type``; ``limit`` takes the head of the finished table.  Not offered: the streaming and
+    Arrow-stream entries, several devices, ``median`` and other order statistics."""
+    mo, f1, f2 = _validate_overlap_thresholds(min_overlap, min_frac1, min_frac2)
+    on_cols = _validate_overlap_input(cols1, cols2, on_cols, ("_1", "_2"), output_type)
+    _check_on_cols_present(on_cols, df1, df2)
+    zero_based = validate_coordinate_systems(df1, df2)
+    c2 = list(DEFAULT_INTERVAL_COLUMNS if cols2 is None else cols2)
+    t1, t2, probe, build, n_contigs, _keys = _prepare(df1, df2, cols1, cols2, on_cols)
+    names, single = _signal_values(value, t2, c2, on_cols, False)
+    taken = set(t1.column_names)
+    for name in names:
+        for stat in _SIGNAL_STATS:
+            out = stat if single else f"{stat}_{name}"
+            if out in taken:
+                raise ValueError(f"value: the output column '{out}' of column '{name}' collides with a column of df1 or another output column")
+            taken.add(out)
+    eng = _map_engine("signal_summary", "overlap_wagg")
+    pm, bm = _threshold_minima(probe, build, zero_based, f1, f2)
+    ops = ["sum", "min", "max", "mean", "count"]
+    inputs = [(*_agg_input(t2, name, None), ops) for name in names]
+    results = eng.overlap_wagg(probe, build, strict=zero_based, n_contigs=n_contigs, agg=inputs, min_overlap=mo, probe_min=pm, build_min=bm)
+    size = np.maximum(np.asarray(probe[2], np.int64) - np.asarray(probe[1], np.int64) + (0 if zero_based else 1), 0)
+    no_size = size == 0
+    table = t1
+    for name, res in zip(names, results):
+        rest = _agg_outputs(name, ["mean", "min", "max"], t2.schema.field(name).type, res)
+        total = res["sum"]
+        mean0 = np.divide(total.astype(np.float64), size.astype(np.float64), out=np.zeros(len(size), np.float64), where=~no_size)
+        columns = {"size": pa.array(size, type=pa.int64()), "bases": pa.array(res["count"], type=pa.int64()), "sum": pa.array(total),
+                   "mean0": pa.array(mean0, type=pa.float64(), mask=no_size if no_size.any() else None),
+                   "mean": rest[f"{name}_mean"], "min": rest[f"{name}_min"], "max": rest[f"{name}_max"]}
+        for stat in _SIGNAL_STATS:
+            table = table.append_column(stat if single else f"{stat}_{name}", columns[stat])
+    return _finish_eager(table, output_type, zero_based, limit)
+
+
+def signal_profile(
+    df1,
+    df2,
+    value,
+    n_bins: int = 100,
+    anchor: Union[str, None] = None,
+    upstream: int = 0,
+    downstream: int = 0,
+    direction_col: Union[str, None] = None,
+    on_cols: Union[list, None] = None,
+    cols1: Union[list, None] = ["chrom", "start", "end"],
+    cols2: Union[list, None] = ["chrom", "start", "end"],
+    output: str = "mean",
+    output_type: str = "polars.LazyFrame",
+):
+    """Binned signal of a track across every df1 row: the rows x ``n_bins`` matrix of deepTools ``computeMatrix`` over a
+    bedGraph-like df2 of (chrom, start, end, ``value``) rows, made on the device from the window of each df1 row -- no frame of
+    bins is built.
+
+    Windows, bins, ``anchor`` / ``upstream`` / ``downstream``, ``direction_col``, ``on_cols``, the int32-range check and the
+    shape of the result (df1's columns plus ``profile``: ``fixed_size_list[n_bins]``, or the bare matrix with
+    ``output_type="numpy.ndarray"``) are ``depth_profile``'s.  Every bin is summarised as ``signal_summary`` summarises a df1
+    row: a df2 row contributes to a bin iff it shares ov >= 1 positions with it and its value is not null.  ``output``:
+
+      ``"mean"``   Float64 sum of value * ov / sum of ov; null (NaN in the matrix) where no signal reaches the bin -- deepTools'
+                   default
+      ``"mean0"``  Float64 sum of value * ov / bin length; null for an empty bin -- ``--missingDataAsZero``
+      ``"sum"``    the sum of value * ov: Int64 (wrapping) for integer columns, Float64 for float columns
+      ``"bases"``  Int64 sum of ov (df2 rows that overlap each other count with their multiplicity)
+      ``"min"`` / ``"max"``  the column's own type over the contributing values; null where there is none (the bare matrix is
+                   Float64 with NaN there)
+
+    One ``value`` column per call (types as in ``signal_summary``).  A row of the ``sum`` / ``bases`` matrix adds up to the
+    window's ``signal_summary``.  The cost is one test per candidate df2 row of every BIN: a df2 row that spans k bins is visited
+    k times, which suits tracks of short rows (bedGraph steps, per-base signal runs), not contig-wide rows.
+
+    Eager.  Not covered: thresholds per bin, streaming inputs or outputs, several devices, ``median``."""
+    n_bins, zero_based, t1, t2, build, n_contigs, on_cols, is_minus, w_start, w_end, windows = _profile_setup(
+        df1, df2, n_bins, anchor, upstream, downstream, direction_col, on_cols, cols1, cols2, output, _SIGNAL_PROFILE_OUTPUTS, output_type)
+    c2 = list(DEFAULT_INTERVAL_COLUMNS if cols2 is None else cols2)
+    (name,), _single = _signal_values(value, t2, c2, on_cols, True)
+    eng = _map_engine("signal_profile", "signal_profile")
+    ops = {"mean": ["mean", "count"], "mean0": ["sum"], "sum": ["sum"], "bases": ["count"], "min": ["min", "count"], "max": ["max", "count"]}[output]
+    (res,) = eng.signal_profile(windows, is_minus, n_bins, build, strict=zero_based, n_contigs=n_contigs,
+                                agg=[(*_agg_input(t2, name, None), ops)])
+    as_matrix = output_type == "numpy.ndarray"
+    if output in ("sum", "bases"):
+        m = res["sum" if output == "sum" else "count"]
+        if as_matrix:
+            return m
+        values = pa.array(m.reshape(-1))
+    elif output == "mean0":
+        lens = profile_bin_lengths(w_start, w_end, zero_based, n_bins, is_minus)
+        null = lens <= 0
+        m = np.divide(res["sum"].astype(np.float64), lens.astype(np.float64), out=np.full(null.shape, np.nan), where=~null)
+        if as_matrix:
+            return m
+        values = pa.array(m.reshape(-1), type=pa.float64(), mask=null.reshape(-1))
+    else:
+        null = res["count"] == 0
+        if as_matrix:
+            return np.where(null, np.nan, res[output].astype(np.float64))
+        if output == "mean":
+            values = pa.array(res["mean"].reshape(-1), type=pa.float64(), mask=null.reshape(-1))
+        else:
+            values = pc.cast(pa.array(np.where(null, 0, res[output]).reshape(-1), mask=null.reshape(-1)), t2.schema.field(name).type)
+    t = t1.append_column("profile", pa.FixedSizeListArray.from_arrays(values, n_bins))
+    return _finish_eager(t, output_type, zero_based, None)
 
 
 PERMUTATION_MAX = (1 << 20) - 1          # the engine takes 2^20 offset rows per call, one of them the observed (all-zero) row
