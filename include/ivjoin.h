@@ -731,6 +731,25 @@ void ivj_segments_free(ivj_segments* s);
 int ivj_multi_inter_dev(ivj_ctx* ctx, ivj_index* const* ix, int32_t n_frames, const ivj_opts* opts, int32_t min_frames, int32_t mode,
                         int64_t capacity, int32_t* contig_dev, int32_t* start_dev, int32_t* end_dev, uint64_t* mask_dev, int64_t* n);
 
+/* ---- N frames pair by pair (pb.pairwise_jaccard) ---------------------------------------------------------------------------------
+ * The two F x F matrices every pairwise similarity of F frames is made of, from ONE walk over all frames (the segments of
+ * IVJ_MULTI_SEGMENTS with min_frames = 1, reduced where they lie in HBM: csrc/pairwise.hip.h), F = n_frames in 1 .. IVJ_MAX_FRAMES:
+ *   bases[i][j] = |U(F_i) & U(F_j)|              the positions both frames cover; bases[i][i] = |U(F_i)|
+ *   runs[i][j]  = the maximal runs of U(F_i) & U(F_j): the regions ivj_setop(IVJ_SETOP_INTERSECTION) of the two frames would return
+ *                 (the n_intersections of ivj_set_stats); runs[i][i] = the union runs of frame i
+ * so that for a pair intersection = bases[i][j], union = bases[i][i] + bases[j][j] - bases[i][j], jaccard = their quotient.  Both are
+ * n_frames * n_frames int64, ROW-MAJOR, full symmetric matrices; exact (a Weak frame [INT32_MIN, INT32_MAX] counts 2^32 positions
+ * per contig; runs <= 2^31); the rows and columns of empty frames, and everything when all frames are empty, are 0.  Conventions
+ * and limits of the frames are those of ivj_multi_inter.  Integer sums in a fixed order, no global atomics: bit-identical from run
+ * to run.  IVJ_EINVAL: n_frames outside 1 .. IVJ_MAX_FRAMES, a NULL frame array or output, an index over another dictionary than
+ * opts->n_contigs.  (New entries change no existing struct or signature: IVJ_ABI_VERSION stays.) */
+/* Host path: `frames` is an array of n_frames sides (an empty side is legal); bases / runs are CALLER-owned host buffers. */
+int ivj_multi_pairwise(ivj_ctx* ctx, const ivj_side* frames, int32_t n_frames, const ivj_opts* opts, int64_t* bases, int64_t* runs);
+/* Device path over n_frames indexes of ivj_index_build_dev (any with_end_order: a missing end order is completed on demand, sweep-only
+ * indexes are accepted; a NULL entry = an empty frame); bases_dev / runs_dev are n_frames * n_frames int64 in HBM.  Waits for the
+ * stream before it returns (the segment list is released). */
+int ivj_multi_pairwise_dev(ivj_ctx* ctx, ivj_index* const* ix, int32_t n_frames, const ivj_opts* opts, int64_t* bases_dev, int64_t* runs_dev);
+
 /* ---- group ids: joins keyed on extra columns (on_cols) --------------------------------------------------------------------------
  * Every kernel partitions by one int32 id per row and ignores ids outside [0, n_contigs).  A dense GROUP id over (chrom, on_col
  * values...) passed as `contig`, with n_contigs = the number of groups, makes every operation of this header run within groups.

@@ -35,6 +35,7 @@
 #include "depth_query.hip.h"
 #include "setop.hip.h"
 #include "multi.hip.h"
+#include "pairwise.hip.h"
 #include "thresh.hip.h"
 #include "select.hip.h"
 #include "merge_agg.hip.h"
@@ -58,6 +59,7 @@ using namespace ivj;
 #include "host_depth_query.hip.h"
 #include "host_setop.hip.h"
 #include "host_multi.hip.h"
+#include "host_pairwise.hip.h"
 #include "host_thresh.hip.h"
 #include "host_select.hip.h"
 #include "host_overlap_agg.hip.h"
@@ -1044,6 +1046,26 @@ void ivj_segments_free(ivj_segments* s) {
     s->contig = s->start = s->end = nullptr; s->mask = nullptr; s->n = 0;
 }
 
+namespace {
+// the frames of a host-path multi-frame call: uploaded and indexed (sweep only + the end order); an empty frame stays without an
+// index (ix[f] stays NULL)
+struct MultiSides {
+    std::vector<DevSide> sides;
+    std::vector<IndexHolder> holders;
+};
+int multi_sides(ivj_ctx* ctx, const ivj_side* frames, int32_t n_frames, const ivj_opts* opts, MultiSides& s, std::vector<ivj_index*>& ix) {
+    s.sides = std::vector<DevSide>((size_t)n_frames);
+    s.holders = std::vector<IndexHolder>((size_t)n_frames);
+    for (int32_t f = 0; f < n_frames; ++f) {
+        if (frames[f].n == 0) continue;
+        IVJ_TRY(upload_side(ctx, &frames[f], s.sides[f]));
+        IVJ_TRY(index_build(ctx, &s.sides[f].s, opts, 3, &s.holders[f].ix));
+        ix[f] = s.holders[f].ix;
+    }
+    return IVJ_OK;
+}
+}  // namespace
+
 int ivj_multi_inter(ivj_ctx* ctx, const ivj_side* frames, int32_t n_frames, const ivj_opts* opts, int32_t min_frames, int32_t mode,
                     ivj_segments* out) try {
     if (!ctx || !out) return fail(IVJ_EINVAL, "ctx or out is NULL");
@@ -1056,15 +1078,8 @@ int ivj_multi_inter(ivj_ctx* ctx, const ivj_side* frames, int32_t n_frames, cons
     // (the indexes do not exist yet: this call only refuses bad n_frames / min_frames / mode before anything is uploaded)
     IVJ_TRY(multi_check(ix.data(), n_frames, opts, min_frames, mode));
     DeviceGuard g(ctx->device);
-    // every frame uploaded and indexed (sweep only + the end order); an empty frame stays without an index
-    std::vector<DevSide> sides((size_t)n_frames);
-    std::vector<IndexHolder> holders((size_t)n_frames);
-    for (int32_t f = 0; f < n_frames; ++f) {
-        if (frames[f].n == 0) continue;
-        IVJ_TRY(upload_side(ctx, &frames[f], sides[f]));
-        IVJ_TRY(index_build(ctx, &sides[f].s, opts, 3, &holders[f].ix));
-        ix[f] = holders[f].ix;
-    }
+    MultiSides s;
+    IVJ_TRY(multi_sides(ctx, frames, n_frames, opts, s, ix));
     DevBuf own;
     int32_t *d_contig = nullptr, *d_start = nullptr, *d_end = nullptr;
     unsigned long long* d_mask = nullptr;
@@ -1085,6 +1100,40 @@ int ivj_multi_inter(ivj_ctx* ctx, const ivj_side* frames, int32_t n_frames, cons
     const hipError_t e = copy.finish();
     if (e != hipSuccess) { ivj_segments_free(out); return fail(IVJ_EHIP, std::string("D2H(segments): ") + hipGetErrorString(e)); }
     out->n = total;
+    return IVJ_OK;
+} IVJ_ABI_CATCH
+
+// ---------------------------------------------------------------- N frames pair by pair (pairwise.hip.h)
+
+int ivj_multi_pairwise_dev(ivj_ctx* ctx, ivj_index* const* ix, int32_t n_frames, const ivj_opts* opts, int64_t* bases_dev, int64_t* runs_dev) try {
+    if (!ctx) return fail(IVJ_EINVAL, "ctx is NULL");
+    IVJ_TRY(check_opts(opts));
+    DeviceGuard g(ctx->device);
+    return pairwise_core(ctx, ix, n_frames, opts, bases_dev, runs_dev);
+} IVJ_ABI_CATCH
+
+int ivj_multi_pairwise(ivj_ctx* ctx, const ivj_side* frames, int32_t n_frames, const ivj_opts* opts, int64_t* bases, int64_t* runs) try {
+    if (!ctx || !bases || !runs) return fail(IVJ_EINVAL, "ctx, bases or runs is NULL");
+    IVJ_TRY(check_opts(opts));
+    if (n_frames < 1 || n_frames > IVJ_MAX_FRAMES || !frames)
+        return fail(IVJ_EINVAL, "multi_pairwise: n_frames must be in 1 .. " + std::to_string(IVJ_MAX_FRAMES) + " and frames not NULL");
+    for (int32_t f = 0; f < n_frames; ++f) IVJ_TRY(check_side(&frames[f], "frame"));
+    std::vector<ivj_index*> ix((size_t)n_frames, nullptr);
+    DeviceGuard g(ctx->device);
+    MultiSides s;
+    IVJ_TRY(multi_sides(ctx, frames, n_frames, opts, s, ix));
+    const size_t bytes = (size_t)n_frames * (size_t)n_frames * 8;
+    DevBuf out;
+    hipError_t e = hipMalloc(&out.p, 2 * align_up(bytes));
+    if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(pairwise matrices): ") + hipGetErrorString(e));
+    int64_t* d_bases = (int64_t*)out.p;
+    int64_t* d_runs = (int64_t*)((char*)out.p + align_up(bytes));
+    IVJ_TRY(pairwise_core(ctx, ix.data(), n_frames, opts, d_bases, d_runs));
+    HostXfer copy(ctx->stream, &ctx->xfer);
+    copy.d2h(bases, d_bases, bytes);
+    copy.d2h(runs, d_runs, bytes);
+    e = copy.finish();
+    if (e != hipSuccess) return fail(IVJ_EHIP, std::string("D2H(pairwise matrices): ") + hipGetErrorString(e));
     return IVJ_OK;
 } IVJ_ABI_CATCH
 

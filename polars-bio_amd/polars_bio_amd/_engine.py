@@ -40,7 +40,7 @@ ABI_SYMBOLS = [
     "ivj_overlap_bases", "ivj_overlap_bases_dev", "ivj_depth_profile", "ivj_depth_profile_dev",
     "ivj_depth", "ivj_blocks_free", "ivj_depth_dev", "ivj_depth_summary", "ivj_depth_summary_dev",
     "ivj_setop", "ivj_regions_free", "ivj_set_stats", "ivj_setop_dev", "ivj_set_stats_dev",
-    "ivj_multi_inter", "ivj_segments_free", "ivj_multi_inter_dev",
+    "ivj_multi_inter", "ivj_segments_free", "ivj_multi_inter_dev", "ivj_multi_pairwise", "ivj_multi_pairwise_dev",
     "ivj_stream_open", "ivj_stream_submit", "ivj_stream_flush", "ivj_stream_set_nearest_ignore", "ivj_stream_close",
     "ivj_dev_alloc", "ivj_dev_free", "ivj_memcpy_h2d", "ivj_memcpy_d2h",
     "ivj_comm_unique_id", "ivj_comm_create", "ivj_comm_create_local", "ivj_comm_destroy", "ivj_comm_info",
@@ -292,6 +292,8 @@ def load_library() -> C.CDLL:
         L.ivj_segments_free.argtypes = [C.POINTER(_Segments)]
         L.ivj_segments_free.restype = None
         L.ivj_multi_inter_dev.argtypes = [vp, C.POINTER(vp), C.c_int32, O, C.c_int32, C.c_int32, C.c_int64, vp, vp, vp, vp, C.POINTER(C.c_int64)]
+        L.ivj_multi_pairwise.argtypes = [vp, P, C.c_int32, O, vp, vp]
+        L.ivj_multi_pairwise_dev.argtypes = [vp, C.POINTER(vp), C.c_int32, O, vp, vp]
         L.ivj_coverage_dev.argtypes = [vp, vp, P, O, vp]
         L.ivj_overlap_bases.argtypes = [vp, P, P, O, vp]
         L.ivj_overlap_bases_dev.argtypes = [vp, vp, P, O, vp]
@@ -868,6 +870,25 @@ class Engine:
         finally:
             self.L.ivj_segments_free(C.byref(out))
 
+    def multi_pairwise(self, frames, strict: bool, n_contigs: int):
+        """pb.pairwise_jaccard over a list of (contig, start, end) frames: -> (bases, runs), two (F, F) int64 arrays, symmetric;
+        bases[i, j] = the positions frames i and j both cover (the diagonal: what frame i covers), runs[i, j] = the regions of
+        their intersection (set_stats' n_intersections), from one walk over all frames."""
+        frames = list(frames)
+        check_multi(len(frames), 1)
+        sides = (_Side * len(frames))()
+        keep = []
+        for f, frame in enumerate(frames):
+            side, arrays = _host_side(*frame)
+            sides[f] = side
+            keep.append(arrays)
+        o = make_opts(strict, n_contigs)
+        bases = np.zeros((len(frames), len(frames)), np.int64)
+        runs = np.zeros((len(frames), len(frames)), np.int64)
+        _check(self.L, self.L.ivj_multi_pairwise(self.h, sides, len(frames), C.byref(o), bases.ctypes.data, runs.ctypes.data), "ivj_multi_pairwise")
+        del keep
+        return bases, runs
+
     def cluster(self, frame, strict: bool, n_contigs: int, min_dist: int = 0):
         """pb.cluster: -> (cluster id int64, cluster_start, cluster_end) per input row + number of clusters."""
         fs, keep = _host_side(*frame)
@@ -1392,6 +1413,14 @@ class Engine:
             return n.value, False
         _check(self.L, rc, "ivj_multi_inter_dev")
         return n.value, True
+
+    def multi_pairwise_dev(self, indexes, opts: _Opts, bases_ptr: int, runs_ptr: int):
+        """``indexes``: one DeviceIndex (or None = an empty frame) per frame; the pointers: F * F int64 each in HBM, row-major."""
+        indexes = list(indexes)
+        check_multi(len(indexes), 1)
+        handles = (C.c_void_p * len(indexes))(*(None if ix is None else getattr(ix.handle, "value", ix.handle) for ix in indexes))
+        _check(self.L, self.L.ivj_multi_pairwise_dev(self.h, handles, len(indexes), C.byref(opts), C.c_void_p(bases_ptr or None),
+                                                     C.c_void_p(runs_ptr or None)), "ivj_multi_pairwise_dev")
 
     def set_stats_dev(self, ix_a: DeviceIndex, ix_b: DeviceIndex, opts: _Opts):
         """-> (only_a, only_b, both, n_intersections)"""

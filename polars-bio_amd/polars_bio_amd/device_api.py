@@ -616,6 +616,40 @@ class DeviceJoin:
                         ix.close()
         return tuple(t[:n] for t in out)
 
+    def multi_pairwise(self, frames, strict: bool, n_contigs: int, indexes=None, out=None):
+        """N frames (a list of DeviceSide) pair by pair -> (bases, runs), two (F, F) int64 CUDA tensors, symmetric: bases[i, j] =
+        the positions frames i and j both cover (the diagonal: what frame i covers), runs[i, j] = the regions of their
+        intersection (set_stats' n_intersections).  One walk over all frames; only the two matrices are written.  ``indexes``:
+        prebuilt indexes of the frames (None entries = empty frames); ``out``: optional preallocated pair of contiguous int64
+        tensors of F * F elements each (returned viewed as (F, F))."""
+        torch = self.torch
+        frames = list(frames)
+        n_frames = len(frames)
+        check_multi(n_frames, 1)
+        opts = make_opts(strict, n_contigs)
+        own = indexes is None
+        ixs = []
+        try:
+            if own:
+                for side in frames:
+                    ixs.append(self._set_index(side, opts) if side.n else None)
+            else:
+                ixs = list(indexes)
+                if len(ixs) != n_frames:
+                    raise ValueError(f"indexes must hold one entry per frame: {n_frames} frames, {len(ixs)} indexes")
+            if out is None:
+                dev = frames[0].start.device
+                out = tuple(torch.empty((n_frames, n_frames), dtype=torch.int64, device=dev) for _ in range(2))
+            if len(out) != 2 or any(t.dtype != torch.int64 or t.numel() != n_frames * n_frames or not t.is_contiguous() for t in out):
+                raise ValueError(f"out must hold two contiguous int64 tensors of {n_frames * n_frames} elements (bases, runs)")
+            self.engine.multi_pairwise_dev(ixs, opts, out[0].data_ptr(), out[1].data_ptr())
+        finally:
+            if own:
+                for ix in ixs:
+                    if ix is not None:
+                        ix.close()
+        return tuple(t.view(n_frames, n_frames) for t in out)
+
     def subtract(self, left: DeviceSide, right: DeviceSide, strict: bool, n_contigs: int, index=None, out=None):
         """left minus the union of right -> (left row, start, end) int32 tensors of the remaining pieces."""
         torch = self.torch

@@ -22,6 +22,7 @@ _ALIASES = {
     "set_intersect": (range_op.set_intersect, True), "set_union": (range_op.set_union, True), "set_difference": (range_op.set_difference, True),
     "set_symmetric_difference": (range_op.set_symmetric_difference, True), "jaccard": (range_op.jaccard, True),
     "multi_intersect": (range_op.multi_intersect, "frames"), "consensus": (range_op.consensus, "frames"),
+    "pairwise_jaccard": (range_op.pairwise_jaccard, "frames"),
 }
 
 

@@ -28,7 +28,7 @@ from .constants import DEFAULT_INTERVAL_COLUMNS
 logger = logging.getLogger("polars_bio_amd")
 
 __all__ = ["overlap", "overlap_batches", "count_overlaps_batches", "nearest_batches", "nearest", "count_overlaps", "coverage", "mean_depth", "depth_profile", "depth_summary", "merge", "cluster", "complement", "subtract", "map_overlaps", "signal_summary", "signal_profile",
-           "set_intersect", "set_union", "set_difference", "set_symmetric_difference", "jaccard", "multi_intersect", "consensus",
+           "set_intersect", "set_union", "set_difference", "set_symmetric_difference", "jaccard", "multi_intersect", "consensus", "pairwise_jaccard",
            "FilterOp", "RangeOp", "OverlapOutputMode"]
 
 
@@ -1811,6 +1811,59 @@ consensus.__doc__ = """Consensus regions of N frames (DiffBind / GenomicRanges "
 
     Output: (chrom, start: Int64, end: Int64, <on_cols...>), named from ``cols``, in (chrom, on values, start) order -- the
     columns and order of the set operations.""" + _MULTI_DOC
+
+
+PAIRWISE_STATISTICS = ("jaccard", "intersection", "union", "n_intersections", "fraction")
+
+
+def pairwise_jaccard(frames, names: Union[list, None] = None, statistic: str = "jaccard", on_cols: Union[list, None] = None,
+                     cols: Union[list, None] = ["chrom", "start", "end"], output_type: str = "polars.LazyFrame"):
+    if statistic not in PAIRWISE_STATISTICS:
+        raise ValueError(f"unknown statistic {statistic!r}: one of {list(PAIRWISE_STATISTICS)}")
+    if names is not None:
+        names = _check_names(names, frames, on_cols, cols)
+    as_matrix = output_type == "numpy.ndarray"
+    _k, on_cols, cols, zero_based, _t1, sides, n_contigs, _dictionary, _gchrom, _dicts = _multi_frames(
+        frames, 1, on_cols, cols, "pyarrow.Table" if as_matrix else output_type)
+    bases, runs = default_engine().multi_pairwise(sides, strict=zero_based, n_contigs=n_contigs)
+    n = len(sides)
+    own = np.diagonal(bases)
+    union = own[:, None] + own[None, :] - bases
+    if as_matrix:
+        if statistic == "intersection":
+            return bases
+        if statistic == "union":
+            return union
+        if statistic == "n_intersections":
+            return runs
+        den = union if statistic == "jaccard" else np.broadcast_to(own[:, None], bases.shape)
+        res = np.full(bases.shape, np.nan)
+        np.divide(bases, den, out=res, where=den != 0)
+        return res
+    labels = pa.array(names, type=pa.string()) if names is not None else pa.array(np.arange(n, dtype=np.int64))
+    first, second = np.repeat(np.arange(n), n), np.tile(np.arange(n), n)
+    inter, uni = bases.reshape(-1), union.reshape(-1)
+    res = pa.table({"frame_1": labels.take(pa.array(first)), "frame_2": labels.take(pa.array(second)),
+                    "intersection": pa.array(inter, type=pa.int64()), "union": pa.array(uni, type=pa.int64()),
+                    "jaccard": pa.array([int(i) / int(u) if u else None for i, u in zip(inter, uni)], type=pa.float64()),
+                    "n_intersections": pa.array(runs.reshape(-1), type=pa.int64())})
+    return A.from_arrow(res, output_type, zero_based)
+
+
+pairwise_jaccard.__doc__ = """How similar is every frame to every other: ``jaccard`` for all F^2 ordered pairs of the F frames from
+    ONE walk over all of them (the "Jaccard statistic for all pairwise comparisons" heat map of bedtools, ``intervene pairwise``,
+    DiffBind's overlap correlation) instead of F (F - 1) / 2 ``jaccard`` calls.
+
+    Output, the long form, pivot-ready: one row per ordered pair in row-major order -- ``frame_1``, ``frame_2`` (the ``names``, one
+    distinct string per frame, or the frames' Int64 positions in the list without them), ``intersection`` (Int64, positions both
+    frames cover), ``union`` (Int64), ``jaccard`` (Float64, intersection / union computed on the host from the two exact integers;
+    null where the union is empty) and ``n_intersections`` (Int64, the regions ``set_intersect`` of the pair would return).  The
+    pair of a frame with itself holds what the frame covers and its merged regions.
+
+    ``output_type="numpy.ndarray"`` returns the bare (F, F) matrix of ``statistic`` instead: "jaccard" (Float64, NaN where the union
+    is empty), "intersection", "union", "n_intersections" (Int64) or "fraction" (Float64, intersection[i, j] / intersection[i, i]:
+    the share of frame i that frame j covers -- not symmetric; NaN for an empty frame i).  With ``on_cols`` the totals are summed
+    over the groups.""" + _MULTI_DOC
 
 
 def cluster(
