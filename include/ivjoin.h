@@ -663,6 +663,35 @@ int ivj_depth_summary(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build
 int ivj_depth_summary_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, const ivj_opts* opts, const int32_t* thresholds,
                           int32_t n_thresholds, int32_t* max_depth_dev, int64_t* bases_ge_dev);
 
+/* pb.depth_histogram / pb.genome_depth_histogram: the distribution of the build side's depth (bedtools genomecov's default output,
+ * bedtools coverage -hist, mosdepth's dist), with d(c, x), the conventions and Q of ivj_depth_summary above, D = max_depth in
+ * [1, IVJ_MAX_HIST_DEPTH] and max_depth + 1 bins per row (at most 8 KiB):
+ *   region form, per probe row q      hist[q][d] = |{x in Q : d(c, x) == d}| for 0 <= d < D,  hist[q][D] = |{x in Q : d(c, x) >= D}|
+ *   contig form, per contig c         hist[c][d] = the same count over all positions of contig c for 1 <= d <= D,  hist[c][0] = 0
+ * (the library does not know a contig's length: the caller fills bin 0 of the contig form).  Both are int64, ROW-major: probe->n
+ * resp. opts->n_contigs rows of max_depth + 1.  A row of the region form sums to |Q|, bin 0 holds its uncovered positions; a
+ * probe that covers no position or lies outside the dictionary gets a row of zeros.  An empty build side, or one whose blocks
+ * come out empty, gives zeros, except bin 0 of the region form, which is |Q|.  Identities: with hist of the region form,
+ * sum over d >= T of hist[q][d] = bases_ge[T] of ivj_depth_summary for T <= D (T = 1: ivj_coverage); when D exceeds every depth,
+ * sum over d of d * hist[q][d] = ivj_overlap_bases and the highest non-zero bin = max_depth of ivj_depth_summary; summing the
+ * contig form's rows gives the histogram of the blocks of ivj_depth.  IVJ_EINVAL: max_depth outside its range and hist NULL
+ * (whatever the row count).  No capacity protocol; integer adds only: bit-identical from run to run.
+ * (New entries change no existing struct or signature: IVJ_ABI_VERSION stays.) */
+#define IVJ_MAX_HIST_DEPTH 1023
+/* The region form's kernel gives a workgroup P = floor(IVJ_HIST_LDS_BYTES / ((max_depth + 1) * 8)) consecutive probe rows,
+ * clamped to [1, IVJ_HIST_MAX_TILE] (informative: the result does not depend on it). */
+#define IVJ_HIST_LDS_BYTES 65536
+#define IVJ_HIST_MAX_TILE 512
+int ivj_depth_hist(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, int32_t max_depth, int64_t* hist);
+int ivj_depth_hist_contigs(ivj_ctx* ctx, const ivj_side* frame, const ivj_opts* opts, int32_t max_depth, int64_t* hist);
+/* The same on an index of ivj_index_build_dev (any form: a missing end order is completed on demand, a sweep-only index is
+ * accepted, as ivj_depth_summary_dev); probe columns and hist in HBM.  Every call derives the depth blocks and, for the region
+ * form, their index and 16-byte records, walks the blocks under each row once, and releases them before it returns (it waits for
+ * the stream): nothing is cached on the index, and nothing but the output grows with max_depth.  partition_mode 0, 1 and 2 all
+ * run in probe order and return identical arrays.  The blocks (at most 2 n) must fit the index limit of ivj_index_build_dev. */
+int ivj_depth_hist_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, const ivj_opts* opts, int32_t max_depth, int64_t* hist_dev);
+int ivj_depth_hist_contigs_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_opts* opts, int32_t max_depth, int64_t* hist_dev);
+
 /* ---- set operations on two frames, and their stats (pb.set_intersect / set_union / set_difference / set_symmetric_difference,
  * pb.jaccard) ------------------------------------------------------------------------------------------------------------------
  * U(F) = the (contig, position) pairs at least one row of F covers, under the conventions of ivj_depth: Strict rows cover

@@ -33,6 +33,7 @@
 #include "depth_sum.hip.h"
 #include "depth_profile.hip.h"
 #include "depth_query.hip.h"
+#include "depth_hist.hip.h"
 #include "setop.hip.h"
 #include "multi.hip.h"
 #include "pairwise.hip.h"
@@ -57,6 +58,7 @@ using namespace ivj;
 #include "host_depth_sum.hip.h"
 #include "host_depth_profile.hip.h"
 #include "host_depth_query.hip.h"
+#include "host_depth_hist.hip.h"
 #include "host_setop.hip.h"
 #include "host_multi.hip.h"
 #include "host_pairwise.hip.h"
@@ -947,6 +949,72 @@ int ivj_depth_summary(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build
     HostXfer copy(ctx->stream, &ctx->xfer);
     if (d_md) copy.d2h(max_depth, d_md, n * 4);
     if (d_bg) copy.d2h(bases_ge, d_bg, (size_t)n_thresholds * col_bytes);
+    HIP_TRY(copy.finish());
+    return IVJ_OK;
+} IVJ_ABI_CATCH
+
+// ---------------------------------------------------------------- depth histogram (positions at each depth, per row / per contig)
+
+int ivj_depth_hist_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, const ivj_opts* opts, int32_t max_depth, int64_t* hist_dev) try {
+    if (!ctx || !ix) return fail(IVJ_EINVAL, "ctx or index is NULL");
+    IVJ_TRY(check_opts(opts));
+    IVJ_TRY(check_side(probe_dev, "probe"));
+    IVJ_TRY(depth_hist_check(max_depth, hist_dev));
+    DeviceGuard g(ctx->device);
+    return depth_hist_dev(ctx, ix, probe_dev, opts, max_depth, hist_dev);
+} IVJ_ABI_CATCH
+
+int ivj_depth_hist(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, int32_t max_depth, int64_t* hist) try {
+    if (!ctx) return fail(IVJ_EINVAL, "ctx is NULL");
+    IVJ_TRY(check_opts(opts));
+    IVJ_TRY(check_side(probe, "probe"));
+    IVJ_TRY(check_side(build, "build"));
+    IVJ_TRY(depth_hist_check(max_depth, hist));
+    if (probe->n == 0) return IVJ_OK;
+    DeviceGuard g(ctx->device);
+    DevSide dp, db;
+    IVJ_TRY(upload_side(ctx, build, db));
+    IVJ_TRY(upload_side(ctx, probe, dp));
+    IndexHolder h;
+    IVJ_TRY(index_build(ctx, &db.s, opts, 3, &h.ix));      // sweep only (no lookup tables) + the end order: what depth_core reads
+    const size_t bytes = (size_t)probe->n * (size_t)(max_depth + 1) * 8;
+    DevBuf out;
+    const hipError_t e = hipMalloc(&out.p, bytes);
+    if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(depth histogram): ") + hipGetErrorString(e));
+    IVJ_TRY(depth_hist_dev(ctx, h.ix, &dp.s, opts, max_depth, (int64_t*)out.p));
+    HostXfer copy(ctx->stream, &ctx->xfer);
+    copy.d2h(hist, out.p, bytes);
+    HIP_TRY(copy.finish());
+    return IVJ_OK;
+} IVJ_ABI_CATCH
+
+int ivj_depth_hist_contigs_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_opts* opts, int32_t max_depth, int64_t* hist_dev) try {
+    if (!ctx || !ix) return fail(IVJ_EINVAL, "ctx or index is NULL");
+    IVJ_TRY(check_opts(opts));
+    IVJ_TRY(depth_hist_check(max_depth, hist_dev));
+    DeviceGuard g(ctx->device);
+    return depth_hist_contigs_dev(ctx, ix, opts, max_depth, hist_dev);
+} IVJ_ABI_CATCH
+
+int ivj_depth_hist_contigs(ivj_ctx* ctx, const ivj_side* frame, const ivj_opts* opts, int32_t max_depth, int64_t* hist) try {
+    if (!ctx) return fail(IVJ_EINVAL, "ctx is NULL");
+    IVJ_TRY(check_opts(opts));
+    IVJ_TRY(check_side(frame, "frame"));
+    IVJ_TRY(depth_hist_check(max_depth, hist));
+    if (opts->n_contigs <= 0) return IVJ_OK;
+    const size_t bytes = (size_t)opts->n_contigs * (size_t)(max_depth + 1) * 8;
+    if (frame->n == 0) { std::memset(hist, 0, bytes); return IVJ_OK; }
+    DeviceGuard g(ctx->device);
+    DevSide ds;
+    IVJ_TRY(upload_side(ctx, frame, ds));
+    IndexHolder h;
+    IVJ_TRY(index_build(ctx, &ds.s, opts, 3, &h.ix));      // sweep only (no lookup tables) + the end order
+    DevBuf out;
+    const hipError_t e = hipMalloc(&out.p, bytes);
+    if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(depth histogram): ") + hipGetErrorString(e));
+    IVJ_TRY(depth_hist_contigs_dev(ctx, h.ix, opts, max_depth, (int64_t*)out.p));
+    HostXfer copy(ctx->stream, &ctx->xfer);
+    copy.d2h(hist, out.p, bytes);
     HIP_TRY(copy.finish());
     return IVJ_OK;
 } IVJ_ABI_CATCH

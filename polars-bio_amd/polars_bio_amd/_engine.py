@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     "ivj_overlap_wagg", "ivj_overlap_wagg_dev", "ivj_signal_profile", "ivj_signal_profile_dev",
     "ivj_overlap_bases", "ivj_overlap_bases_dev", "ivj_depth_profile", "ivj_depth_profile_dev",
     "ivj_depth", "ivj_blocks_free", "ivj_depth_dev", "ivj_depth_summary", "ivj_depth_summary_dev",
+    "ivj_depth_hist", "ivj_depth_hist_contigs", "ivj_depth_hist_dev", "ivj_depth_hist_contigs_dev",
     "ivj_setop", "ivj_regions_free", "ivj_set_stats", "ivj_setop_dev", "ivj_set_stats_dev",
     "ivj_multi_inter", "ivj_segments_free", "ivj_multi_inter_dev", "ivj_multi_pairwise", "ivj_multi_pairwise_dev",
     "ivj_stream_open", "ivj_stream_submit", "ivj_stream_flush", "ivj_stream_set_nearest_ignore", "ivj_stream_close",
@@ -58,6 +59,13 @@ STREAM_OVERLAP, STREAM_COUNT, STREAM_NEAREST = 0, 1, 2
 # ivj_opts.nearest_ignore: the candidate classes a nearest call leaves out (rows before / after the probe; overlapping rows always count)
 NEAREST_IGNORE_LEFT, NEAREST_IGNORE_RIGHT = 1, 2
 DEPTH_PROFILE_MAX_BINS = 4096        # include/ivjoin.h: ivj_depth_profile accepts 1 .. this many bins
+MAX_HIST_DEPTH = 1023                # include/ivjoin.h: IVJ_MAX_HIST_DEPTH, ivj_depth_hist accepts max_depth in 1 .. this
+HIST_LDS_BYTES, HIST_MAX_TILE = 65536, 512      # include/ivjoin.h: IVJ_HIST_LDS_BYTES, IVJ_HIST_MAX_TILE
+
+
+def depth_hist_tile(max_depth: int) -> int:
+    """probe rows one workgroup of ivj_depth_hist owns (include/ivjoin.h); informative: the result does not depend on it"""
+    return min(max(HIST_LDS_BYTES // ((int(max_depth) + 1) * 8), 1), HIST_MAX_TILE)
 
 # the operations of ivj_setop / ivj_setop_dev (include/ivjoin.h: IVJ_SETOP_*)
 SETOP_INTERSECTION, SETOP_UNION, SETOP_DIFFERENCE, SETOP_SYMMETRIC_DIFFERENCE = 0, 1, 2, 3
@@ -301,6 +309,10 @@ def load_library() -> C.CDLL:
         L.ivj_depth_profile_dev.argtypes = [vp, vp, P, vp, C.c_int32, O, vp]
         L.ivj_depth_summary.argtypes = [vp, P, P, O, vp, C.c_int32, vp, vp]
         L.ivj_depth_summary_dev.argtypes = [vp, vp, P, O, vp, C.c_int32, vp, vp]
+        L.ivj_depth_hist.argtypes = [vp, P, P, O, C.c_int32, vp]
+        L.ivj_depth_hist_contigs.argtypes = [vp, P, O, C.c_int32, vp]
+        L.ivj_depth_hist_dev.argtypes = [vp, vp, P, O, C.c_int32, vp]
+        L.ivj_depth_hist_contigs_dev.argtypes = [vp, vp, O, C.c_int32, vp]
         L.ivj_stream_open.argtypes = [vp, P, O, C.c_int, C.c_int64, C.POINTER(vp)]
         L.ivj_stream_submit.argtypes = [vp, P, C.POINTER(_StreamResult)]
         L.ivj_stream_flush.argtypes = [vp, C.POINTER(_StreamResult)]
@@ -958,6 +970,36 @@ class Engine:
         del keep_p, keep_b
         return md, bg
 
+    def depth_hist(self, probe, build, strict: bool, n_contigs: int, max_depth: int, partition_mode: int = 0) -> np.ndarray:
+        """pb.depth_histogram: -> int64 (n, max_depth + 1), probe order: bin d of a row = its positions that exactly d build rows of
+        its contig cover, the last bin = max_depth or more; a row sums to its positions, bin 0 holds the uncovered ones."""
+        ps, keep_p = _host_side(*probe)
+        bs, keep_b = _host_side(*build)
+        o = make_opts(strict, n_contigs, partition_mode=partition_mode)
+        max_depth = int(max_depth)
+        # a depth the entry refuses gets no matrix: the entry checks max_depth before it looks at the output
+        ok = 1 <= max_depth <= MAX_HIST_DEPTH
+        hist = np.empty((ps.n, max_depth + 1 if ok else 0), np.int64)
+        keep = hist if hist.size else np.empty(1, np.int64)          # (an array without elements still has to pass a non-NULL address)
+        _check(self.L, self.L.ivj_depth_hist(self.h, C.byref(ps), C.byref(bs), C.byref(o), max_depth, keep.ctypes.data if ok else None),
+               "ivj_depth_hist")
+        del keep_p, keep_b
+        return hist
+
+    def depth_hist_contigs(self, frame, strict: bool, n_contigs: int, max_depth: int) -> np.ndarray:
+        """pb.genome_depth_histogram: -> int64 (n_contigs, max_depth + 1): bin d >= 1 of a contig = its positions that exactly d rows
+        of the frame cover, the last bin = max_depth or more; bin 0 is 0 (the engine does not know a contig's length)."""
+        fs, keep_f = _host_side(*frame)
+        o = make_opts(strict, n_contigs)
+        max_depth = int(max_depth)
+        ok = 1 <= max_depth <= MAX_HIST_DEPTH
+        hist = np.empty((int(n_contigs), max_depth + 1 if ok else 0), np.int64)
+        keep = hist if hist.size else np.empty(1, np.int64)
+        _check(self.L, self.L.ivj_depth_hist_contigs(self.h, C.byref(fs), C.byref(o), max_depth, keep.ctypes.data if ok else None),
+               "ivj_depth_hist_contigs")
+        del keep_f
+        return hist
+
     def _pieces(self, fn, name, a, b, strict, n_contigs, partition_mode=0):
         sa, keep_a = _host_side(*a)
         sb, keep_b = _host_side(*b)
@@ -1449,6 +1491,16 @@ class Engine:
         k = int(thr.shape[0])
         _check(self.L, self.L.ivj_depth_summary_dev(self.h, ix.handle, C.byref(probe), C.byref(opts), thr.ctypes.data if k else None, k,
                                                      C.c_void_p(max_depth_ptr or None), C.c_void_p(bases_ge_ptr or None)), "ivj_depth_summary_dev")
+
+    def depth_hist_dev(self, ix: DeviceIndex, probe: _Side, opts: _Opts, max_depth: int, hist_ptr: int):
+        """hist_ptr: device address (0 = NULL) of row-major int64[n, max_depth + 1]."""
+        _check(self.L, self.L.ivj_depth_hist_dev(self.h, ix.handle, C.byref(probe), C.byref(opts), int(max_depth), C.c_void_p(hist_ptr or None)),
+               "ivj_depth_hist_dev")
+
+    def depth_hist_contigs_dev(self, ix: DeviceIndex, opts: _Opts, max_depth: int, hist_ptr: int):
+        """hist_ptr: device address (0 = NULL) of row-major int64[n_contigs, max_depth + 1]."""
+        _check(self.L, self.L.ivj_depth_hist_contigs_dev(self.h, ix.handle, C.byref(opts), int(max_depth), C.c_void_p(hist_ptr or None)),
+               "ivj_depth_hist_contigs_dev")
 
     def permute_overlaps_dev(self, ix: DeviceIndex, probe: _Side, opts: _Opts, contig_len_ptr: int, offsets_ptr: int, n_perm: int,
                              n_pairs_ptr: int, n_rows_ptr: int):

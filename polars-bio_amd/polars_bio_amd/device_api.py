@@ -468,6 +468,51 @@ class DeviceJoin:
                 ix.close()
         return md, bg
 
+    def depth_histogram(self, probe: DeviceSide, build: DeviceSide, strict: bool, n_contigs: int, max_depth: int, index=None, out=None,
+                        partition_mode: int = 0):
+        """Per probe row the number of its positions at each depth 0 .. max_depth of the build side (the last bin: max_depth or
+        more) -> int64 tensor (probe.n, max_depth + 1) in HBM; a row sums to its positions.  ``index``: a prebuilt index of the
+        build side (any form); ``out``: a contiguous int64 tensor of that shape."""
+        torch = self.torch
+        max_depth = int(max_depth)
+        opts = make_opts(strict, n_contigs, partition_mode=partition_mode)
+        bins = max_depth + 1 if max_depth >= 0 else 0
+        if out is not None and (out.dtype != torch.int64 or tuple(out.shape) != (probe.n, bins) or not out.is_contiguous()):
+            raise ValueError("out must be a contiguous int64 tensor of shape (probe.n, max_depth + 1)")
+        own = index is None
+        ix = self.engine.index_build_dev(build.as_c(), opts, True, sweep_only=True) if own else index
+        try:
+            hist = out if out is not None else torch.empty((probe.n, bins), dtype=torch.int64, device=probe.start.device)
+            # (a tensor without elements has no address, and the entry refuses a NULL output whatever the row count)
+            spare = hist if hist.numel() else torch.empty(1, dtype=torch.int64, device=probe.start.device)
+            self.engine.depth_hist_dev(ix, probe.as_c(), opts, max_depth, spare.data_ptr())
+        finally:
+            if own:
+                ix.close()
+        return hist
+
+    def depth_histogram_contigs(self, frame: DeviceSide, strict: bool, n_contigs: int, max_depth: int, index=None, out=None):
+        """Per contig the number of positions at each depth 1 .. max_depth of the frame (the last bin: max_depth or more; bin 0 is
+        0, the engine does not know a contig's length) -> int64 tensor (n_contigs, max_depth + 1) in HBM.  ``index`` / ``out`` as
+        in ``depth_histogram``."""
+        torch = self.torch
+        max_depth = int(max_depth)
+        opts = make_opts(strict, n_contigs)
+        bins = max_depth + 1 if max_depth >= 0 else 0
+        if out is not None and (out.dtype != torch.int64 or tuple(out.shape) != (int(n_contigs), bins) or not out.is_contiguous()):
+            raise ValueError("out must be a contiguous int64 tensor of shape (n_contigs, max_depth + 1)")
+        own = index is None
+        ix = self.engine.index_build_dev(frame.as_c(), opts, True, sweep_only=True) if own else index
+        try:
+            dev = frame.start.device
+            hist = out if out is not None else torch.empty((int(n_contigs), bins), dtype=torch.int64, device=dev)
+            spare = hist if hist.numel() else torch.empty(1, dtype=torch.int64, device=dev)
+            self.engine.depth_hist_contigs_dev(ix, opts, max_depth, spare.data_ptr())
+        finally:
+            if own:
+                ix.close()
+        return hist
+
     def merge(self, frame: DeviceSide, strict: bool, n_contigs: int, min_dist: int = 0, out=None, agg=None):
         """Merged intervals of one frame -> (contig, start, end int32, n_intervals int64) tensors.
         ``out``: optional preallocated 4-tuple (views of the first n_merged elements are returned).

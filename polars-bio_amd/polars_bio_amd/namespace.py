@@ -14,11 +14,11 @@ from . import range_op
 _ALIASES = {
     "overlap": (range_op.overlap, True), "nearest": (range_op.nearest, True), "count_overlaps": (range_op.count_overlaps, True),
     "coverage": (range_op.coverage, True), "mean_depth": (range_op.mean_depth, True), "depth_summary": (range_op.depth_summary, True),
-    "depth_profile": (range_op.depth_profile, True),
+    "depth_profile": (range_op.depth_profile, True), "depth_histogram": (range_op.depth_histogram, True),
     "subtract": (range_op.subtract, True), "map_overlaps": (range_op.map_overlaps, True),
     "signal_summary": (range_op.signal_summary, True), "signal_profile": (range_op.signal_profile, True),
     "permutation_test": (range_op.permutation_test, True),
-    "merge": (range_op.merge, False), "depth": (range_op.depth, False), "cluster": (range_op.cluster, False), "complement": (range_op.complement, False),
+    "merge": (range_op.merge, False), "depth": (range_op.depth, False), "genome_depth_histogram": (range_op.genome_depth_histogram, False), "cluster": (range_op.cluster, False), "complement": (range_op.complement, False),
     "set_intersect": (range_op.set_intersect, True), "set_union": (range_op.set_union, True), "set_difference": (range_op.set_difference, True),
     "set_symmetric_difference": (range_op.set_symmetric_difference, True), "jaccard": (range_op.jaccard, True),
     "multi_intersect": (range_op.multi_intersect, "frames"), "consensus": (range_op.consensus, "frames"),

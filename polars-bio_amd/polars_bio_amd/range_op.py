@@ -27,7 +27,7 @@ from .constants import DEFAULT_INTERVAL_COLUMNS
 
 logger = logging.getLogger("polars_bio_amd")
 
-__all__ = ["overlap", "overlap_batches", "count_overlaps_batches", "nearest_batches", "nearest", "count_overlaps", "coverage", "mean_depth", "depth_profile", "depth_summary", "merge", "cluster", "complement", "subtract", "map_overlaps", "signal_summary", "signal_profile",
+__all__ = ["overlap", "overlap_batches", "count_overlaps_batches", "nearest_batches", "nearest", "count_overlaps", "coverage", "mean_depth", "depth_profile", "depth_summary", "depth_histogram", "genome_depth_histogram", "merge", "cluster", "complement", "subtract", "map_overlaps", "signal_summary", "signal_profile",
            "set_intersect", "set_union", "set_difference", "set_symmetric_difference", "jaccard", "multi_intersect", "consensus", "pairwise_jaccard",
            "FilterOp", "RangeOp", "OverlapOutputMode"]
 
@@ -1021,6 +1021,177 @@ def depth_summary(
     for k, thr in enumerate(thresholds):
         t = t.append_column(f"bases_ge_{thr}", pa.array(bases_ge[k], type=pa.int64()))
     return A.from_arrow(t, output_type, zero_based)
+
+
+def _validate_max_depth(max_depth) -> int:
+    from ._engine import MAX_HIST_DEPTH
+    if isinstance(max_depth, (bool, np.bool_)) or not isinstance(max_depth, (int, np.integer)) or not 1 <= int(max_depth) <= MAX_HIST_DEPTH:
+        raise ValueError(f"max_depth must be an int in 1 .. {MAX_HIST_DEPTH}, got {max_depth!r}")
+    return int(max_depth)
+
+
+def _histogram_engine(what: str):
+    eng = default_engine()
+    if not hasattr(eng, "depth_hist") or not hasattr(eng, "depth_hist_contigs"):
+        raise NotImplementedError(f"{what} needs a single-device engine; the default engine is a {type(eng).__name__} "
+                                  "(several devices), which has no histogram kernel")
+    return eng
+
+
+def depth_histogram(
+    df1,
+    df2,
+    max_depth: int = 100,
+    output: str = "bases",
+    cumulative: bool = False,
+    suffixes: tuple = ("_1", "_2"),
+    on_cols: Union[list, None] = None,
+    cols1: Union[list, None] = ["chrom", "start", "end"],
+    cols2: Union[list, None] = ["chrom", "start", "end"],
+    output_type: str = "polars.LazyFrame",
+):
+    """The distribution of df2's depth over every df1 interval: bin d of a row = the number of its positions that exactly d df2
+    intervals of its contig cover, d = 0 .. ``max_depth`` - 1, and the last bin = the positions covered ``max_depth`` deep or
+    deeper.  ``bedtools coverage -hist`` per target region and mosdepth's per-region distribution, in one call, with as many bins
+    as wanted (``max_depth`` in 1 .. 1023) where ``depth_summary`` takes 8 thresholds.
+
+    A row sums to its number of positions; bin 0 holds the uncovered ones.  Identities: the sum of the bins d >= T =
+    ``depth_summary``'s ``bases_ge_<T>`` (T = 1: ``pb.coverage``); when ``max_depth`` exceeds every depth, the sum of d * bin d =
+    ``pb.mean_depth``'s ``bases``.
+
+    Output = df1 columns + ``histogram``, an Arrow ``fixed_size_list<...>[max_depth + 1]``, df1 row order kept.
+    ``output="bases"``: Int64; ``output="fraction"``: Float64, each bin divided by the row's positions, null for a row without
+    a position.  ``cumulative=True`` turns bin d into "depth >= d" (mosdepth's distribution: bin 0 = all positions of the row, resp.
+    1.0).  ``output_type="numpy.ndarray"`` returns the bare (n, max_depth + 1) matrix (NaN for null in the fraction form).
+    0-based frames are half-open, 1-based frames closed.  Rows of either frame that cover no position, and rows with a null
+    chrom, share nothing (such df1 rows get zeros).  ``on_cols``: only df2 intervals of the df1 row's group of equal (chrom, on
+    values) count; a null on-value matches nothing.
+
+    Eager, one device.  Not covered: streaming inputs or outputs, a weighted (signal) histogram, quantiles."""
+    on_cols = _validate_overlap_input(cols1, cols2, on_cols, suffixes, "pyarrow.Table" if output_type == "numpy.ndarray" else output_type)
+    max_depth = _validate_max_depth(max_depth)
+    if output not in ("bases", "fraction"):
+        raise ValueError(f"output must be 'bases' or 'fraction', got {output!r}")
+    _check_on_cols_present(on_cols, df1, df2)
+    zero_based = validate_coordinate_systems(df1, df2)
+    t1, t2, probe, build, n_contigs, _keys = _prepare(df1, df2, cols1, cols2, on_cols)
+    hist = _histogram_engine("depth_histogram").depth_hist(probe, build, strict=zero_based, n_contigs=n_contigs, max_depth=max_depth)
+    positions = hist.sum(axis=1)
+    if cumulative:
+        hist = np.ascontiguousarray(np.cumsum(hist[:, ::-1], axis=1)[:, ::-1])
+    if output == "bases":
+        if output_type == "numpy.ndarray":
+            return hist
+        values = pa.array(hist.reshape(-1), type=pa.int64())
+    else:
+        none = positions <= 0
+        frac = np.divide(hist.astype(np.float64), positions.astype(np.float64)[:, None], out=np.full(hist.shape, np.nan), where=~none[:, None])
+        if output_type == "numpy.ndarray":
+            return frac
+        values = pa.array(frac.reshape(-1), type=pa.float64(), mask=np.repeat(none, max_depth + 1))
+    t = t1.append_column("histogram", pa.FixedSizeListArray.from_arrays(values, max_depth + 1))
+    return _finish_eager(t, output_type, zero_based, None)
+
+
+def genome_depth_histogram(
+    df,
+    genome=None,
+    max_depth: int = 100,
+    on_cols: Union[list, None] = None,
+    cols: Union[list, None] = ["chrom", "start", "end"],
+    output_type: str = "polars.LazyFrame",
+):
+    """The distribution of the frame's depth per contig and over the whole genome: ``bedtools genomecov``'s default table.
+
+    Rows (chrom, <on_cols...>, depth, bases, size, fraction): ``bases`` = the positions of the contig that exactly ``depth`` rows of
+    ``df`` cover, ``size`` = the contig's length, ``fraction`` = bases / size; per contig in sorted-name order, depth ascending, only
+    rows with ``bases`` > 0.  The last bin is labelled ``max_depth`` and means "``max_depth`` or deeper" (``genomecov -max``).  After the
+    contigs a block with chrom = "genome" sums all contigs of ``genome``.
+
+    ``genome``: a {contig: length} dict or a two-column (name, length) frame.  The depth-0 row of a contig is its length minus
+    its covered positions; a contig of ``genome`` that ``df`` never touches gets its single depth-0 row.  A contig of ``df`` that
+    ``genome`` lacks is a ValueError, and so is a row that covers a position outside [0, length) (0-based frames) or
+    [1, length] (1-based frames); the message names the first such row.
+    ``genome=None``: contig lengths are unknown, so there are no depth-0 rows and no ``size`` / ``fraction`` columns, and the final
+    block, the totals over all contigs, is named "all".
+
+    ``on_cols``: the depth per group of equal (chrom, on values), e.g. per strand: rows in (chrom, on values, depth) order, and one
+    "genome" / "all" block per combination of on values that occurs in ``df``; rows with a null on-value are dropped, as rows
+    with a null chrom are.  Rows that cover no position contribute nothing.
+
+    Eager, one device."""
+    on_cols = _validate_overlap_input(cols, cols, on_cols, ("_1", "_2"), output_type)
+    max_depth = _validate_max_depth(max_depth)
+    _check_on_cols_present(on_cols, df)
+    zero_based = validate_coordinate_system_single(df)
+    cols = list(DEFAULT_INTERVAL_COLUMNS if cols is None else cols)
+    t = A.to_arrow(df)
+    side, n_contigs, dictionary = A.encode_frame(t, cols)
+    names = [str(x) for x in pc.cast(dictionary, pa.string()).to_pylist()]            # chrom id -> name, sorted
+    lengths = None
+    if genome is not None:
+        gnames, lengths = _genome_lengths(genome)
+        where = {k: j for j, k in enumerate(gnames)}
+        unknown = [k for k in names if k not in where]
+        if unknown:
+            raise ValueError(f"genome lacks contig {unknown[0]!r} of df" + (f" (and {len(unknown) - 1} more)" if len(unknown) > 1 else ""))
+        to_out = np.array([where[k] for k in names], np.int64)                          # chrom id -> row of the genome
+        c, s, e = (np.asarray(a).astype(np.int64) for a in side)
+        known = c >= 0
+        ln = lengths[to_out[np.where(known, c, 0)]] if len(names) else np.zeros(len(c), np.int64)
+        if zero_based:
+            out_of = known & (s < e) & ((s < 0) | (e > ln))
+        else:
+            out_of = known & (s <= e) & ((s < 1) | (e > ln))
+        bad = np.flatnonzero(out_of)
+        if bad.size:
+            r = int(bad[0])
+            raise ValueError(f"df row {r} ({names[int(c[r])]}: {int(s[r])} .. {int(e[r])}) reaches outside the contig, whose length is {int(ln[r])}"
+                             + (" ([0, length), 0-based)" if zero_based else " ([1, length], 1-based)"))
+        out_names = gnames
+    else:
+        to_out = np.arange(len(names), dtype=np.int64)
+        out_names = names
+    gchrom = dicts = None
+    if on_cols:
+        (codes,), cards, dicts, _ = A.encode_on_cols([t], on_cols)
+        empty = (np.empty(0, np.int32),) * 3
+        _, side, groups, table = A.group_sides(empty, side, n_contigs, [np.empty(0, np.int32)] * len(on_cols), codes, cards, on_cols)
+        n_contigs, gchrom = max(groups, 1), np.asarray(table)[:groups]
+    keep = side[0] >= 0                                   # rows with a null chrom (or on-value) belong to no contig
+    side = tuple(a[keep] for a in side) if not keep.all() else side
+    bins = max_depth + 1
+    hist = _histogram_engine("genome_depth_histogram").depth_hist_contigs(side, strict=zero_based, n_contigs=n_contigs, max_depth=max_depth) if n_contigs > 0 else np.zeros((0, bins), np.int64)
+    # H[contig of the output, combination of on values, depth]
+    if gchrom is None:
+        combos = np.zeros((1, 0), np.int64)
+        H = np.zeros((len(out_names), 1, bins), np.int64)
+        H[to_out, 0, :] = hist[:len(names)]
+    else:
+        combos, which = np.unique(gchrom[:, 1:].astype(np.int64), axis=0, return_inverse=True) if len(gchrom) else (np.zeros((0, len(on_cols)), np.int64), np.zeros(0, np.int64))
+        H = np.zeros((len(out_names), len(combos), bins), np.int64)
+        if len(gchrom):
+            H[to_out[gchrom[:, 0].astype(np.int64)], np.asarray(which).reshape(-1), :] = hist[:len(gchrom)]
+    size = None
+    if lengths is not None:
+        H[:, :, 0] = lengths[:, None] - H[:, :, 1:].sum(axis=2)
+        size = np.broadcast_to(lengths[:, None, None], H.shape)
+    total = H.sum(axis=0, keepdims=True)
+    ci, ki, di = np.nonzero(H)
+    _tc, tk, td = np.nonzero(total)
+    chrom = pa.array([out_names[j] for j in ci] + ["genome" if lengths is not None else "all"] * len(tk), type=pa.string())
+    data = {cols[0]: chrom}
+    for j, name in enumerate(on_cols or ()):
+        code = np.concatenate([combos[ki, j], combos[tk, j]]).astype(np.int32)
+        data[name] = A.cast_on_values(pc.take(dicts[j], pa.array(code, type=pa.int32())), t.schema.field(name).type)
+    bases = np.concatenate([H[ci, ki, di], total[0, tk, td]])
+    data["depth"] = pa.array(np.concatenate([di, td]).astype(np.int64))
+    data["bases"] = pa.array(bases)
+    if lengths is not None:
+        sz = np.concatenate([size[ci, ki, di], np.full(len(tk), int(lengths.sum()), np.int64)])
+        data["size"] = pa.array(sz)
+        data["fraction"] = pa.array(bases.astype(np.float64) / sz.astype(np.float64))
+    return A.from_arrow(pa.table(data), output_type, zero_based)
 
 
 _AGG_OP_NAMES = ("sum", "min", "max", "mean", "count")
