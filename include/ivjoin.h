@@ -692,6 +692,38 @@ int ivj_depth_hist_contigs(ivj_ctx* ctx, const ivj_side* frame, const ivj_opts* 
 int ivj_depth_hist_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, const ivj_opts* opts, int32_t max_depth, int64_t* hist_dev);
 int ivj_depth_hist_contigs_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_opts* opts, int32_t max_depth, int64_t* hist_dev);
 
+/* pb.depth_quantiles / pb.median_depth: exact ORDER STATISTICS of the build side's depth over the positions of every probe row
+ * (the median depth of a region, mosdepth --use-median, and its quartiles), with d(c, x), the conventions and Q of
+ * ivj_depth_summary above.  For a probe row with L = |Q| >= 1 let v[0] <= v[1] <= ... <= v[L - 1] be the depths d(c, x) of its
+ * positions, sorted; uncovered positions are in the list at depth 0.  With n_ranks in [1, IVJ_MAX_QUANT_RANKS] ranks per row:
+ *   out[q][j] = v[ranks[q][j]]   for 0 <= ranks[q][j] < L;   -1 for any other rank, and for a probe that covers no position or
+ *   lies outside the dictionary.
+ * ranks (int64, 0-based) and out (int32) are ROW-major, probe->n rows of n_ranks.  The ranks of a row may come in any order and
+ * repeat.  A quantile is the caller's arithmetic on ranks (q (L - 1), its floor and ceiling): the library answers ranks only.
+ * Exact for any depth up to 2^31 - 1.  An empty build side, or one whose blocks come out empty, gives 0 for every rank inside
+ * [0, L).  Identities: rank L - 1 gives max_depth of ivj_depth_summary; where no depth exceeds max_depth, out[q][j] is the first
+ * bin of ivj_depth_hist's row q whose cumulative count exceeds ranks[q][j].  IVJ_EINVAL: n_ranks outside its range, ranks or out
+ * NULL (whatever the row count).  No capacity protocol; no global atomics, integer adds only: bit-identical from run to run.
+ * (New entries change no existing struct or signature: IVJ_ABI_VERSION stays.) */
+#define IVJ_MAX_QUANT_RANKS 16
+/* The kernel is a radix select over the depth blocks under each row, IVJ_QUANT_BITS bits per pass, with a
+ * 2^IVJ_QUANT_BITS-bin histogram per (row, rank) in LDS; it gives a workgroup
+ * P = floor(IVJ_QUANT_LDS_BYTES / (n_ranks * 2^IVJ_QUANT_BITS * 8)) consecutive probe rows, clamped to [1, IVJ_QUANT_MAX_TILE]
+ * (informative: the result does not depend on them; IVJ_QUANT_BITS may be set when the library is compiled, 4 .. 8). */
+#ifndef IVJ_QUANT_BITS
+#define IVJ_QUANT_BITS 4
+#endif
+#define IVJ_QUANT_LDS_BYTES 65536
+#define IVJ_QUANT_MAX_TILE 512
+int ivj_depth_quantiles(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, int32_t n_ranks,
+                        const int64_t* ranks /* n x n_ranks, row-major, 0-based */, int32_t* out /* n x n_ranks */);
+/* The same on an index of ivj_index_build_dev (any form, as ivj_depth_hist_dev); probe columns, ranks and out in HBM.  Every call
+ * derives the depth blocks, their index and 16-byte records (the steps of ivj_depth_hist_dev), walks the blocks under each tile
+ * of rows once per pass, and releases them before it returns (it waits for the stream): nothing is cached on the index.
+ * partition_mode 0, 1 and 2 all run in probe order and return identical arrays. */
+int ivj_depth_quantiles_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, const ivj_opts* opts, int32_t n_ranks,
+                            const int64_t* ranks_dev, int32_t* out_dev);
+
 /* ---- set operations on two frames, and their stats (pb.set_intersect / set_union / set_difference / set_symmetric_difference,
  * pb.jaccard) ------------------------------------------------------------------------------------------------------------------
  * U(F) = the (contig, position) pairs at least one row of F covers, under the conventions of ivj_depth: Strict rows cover

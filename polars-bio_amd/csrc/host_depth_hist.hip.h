@@ -38,32 +38,49 @@ int depth_hist_tile(int32_t max_depth, size_t budget) {
     return (int)(p < 1 ? 1 : (p > (size_t)IVJ_HIST_MAX_TILE ? (size_t)IVJ_HIST_MAX_TILE : p));
 }
 
-int depth_hist_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe, const ivj_opts* opts, int32_t D, int64_t* hist) {
-    const int64_t n = probe->n;
-    if (n == 0) return IVJ_OK;
-    const bool strict = opts->filter_op == IVJ_FILTER_STRICT;
-    // 1. the blocks, library-owned
+// Steps 1 and 2 of a call of the region form, shared with host_depth_quant.hip.h: the depth blocks of the index, and (when there
+// are any) the index of the blocks and their 16-byte records.  Everything is released with the object; the caller waits for the
+// stream before that.
+struct DepthBlocks {
     DevBuf own;
-    int32_t *bc = nullptr, *bs = nullptr, *be = nullptr, *bd = nullptr;
-    int64_t nb = 0;
-    if (ix->n > 0) IVJ_TRY(depth_core(ctx, ix, opts, -1, &bc, &bs, &be, &bd, &own, &nb));
-    // 2. their index and records (no blocks: every probe row of the dictionary is |Q| in bin 0)
     IndexHolder h;
     int4* rec = nullptr;
-    DqIndex v{nullptr, nullptr, nullptr, nullptr, ix->n_contigs};
+    int64_t nb = 0;
+    DqIndex v{nullptr, nullptr, nullptr, nullptr, 0};
+};
+
+int depth_blocks_build(ivj_ctx* ctx, ivj_index* ix, const ivj_opts* opts, DepthBlocks& B) {
+    // 1. the blocks, library-owned
+    int32_t *bc = nullptr, *bs = nullptr, *be = nullptr, *bd = nullptr;
+    if (ix->n > 0) IVJ_TRY(depth_core(ctx, ix, opts, -1, &bc, &bs, &be, &bd, &B.own, &B.nb));
+    // 2. their index and records (no blocks: every probe row of the dictionary is |Q| in bin 0)
+    const int64_t nb = B.nb;
+    B.v = DqIndex{nullptr, nullptr, nullptr, nullptr, ix->n_contigs};
     if (nb > 0) {
         const ivj_side blocks{bc, bs, be, nb, nullptr};
         ivj_opts o2 = *opts;
         o2.n_contigs = ix->n_contigs;
         o2.partition_mode = 0;
-        IVJ_TRY(index_build(ctx, &blocks, &o2, 3, &h.ix));   // sweep only (no lookup tables) + the end order with the joint grid
+        IVJ_TRY(index_build(ctx, &blocks, &o2, 3, &B.h.ix));   // sweep only (no lookup tables) + the end order with the joint grid
         const int64_t pad0 = (nb + 15) & ~(int64_t)15;
         IVJ_TRY(arena_reserve(ctx, align_up((size_t)nb * 16) + align_up((size_t)pad0 * 4) + 4096));
-        rec = arena_take<int4>(ctx, nb);
+        B.rec = arena_take<int4>(ctx, nb);
         int32_t* level0 = arena_take<int32_t>(ctx, pad0);
-        LAUNCH(ctx, "depth_hist_records", k_dq_records, grid1d(pad0, 256), 256, (const int32_t*)bs, (const int32_t*)be, (const int32_t*)bd, nb, pad0, rec, level0);
-        v = DqIndex{h.ix->cmeta_j, h.ix->crec, h.ix->b_start, h.ix->e_end, h.ix->n_contigs};
+        LAUNCH(ctx, "depth_hist_records", k_dq_records, grid1d(pad0, 256), 256, (const int32_t*)bs, (const int32_t*)be, (const int32_t*)bd, nb, pad0, B.rec, level0);
+        B.v = DqIndex{B.h.ix->cmeta_j, B.h.ix->crec, B.h.ix->b_start, B.h.ix->e_end, B.h.ix->n_contigs};
     }
+    return IVJ_OK;
+}
+
+int depth_hist_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe, const ivj_opts* opts, int32_t D, int64_t* hist) {
+    const int64_t n = probe->n;
+    if (n == 0) return IVJ_OK;
+    const bool strict = opts->filter_op == IVJ_FILTER_STRICT;
+    DepthBlocks B;
+    IVJ_TRY(depth_blocks_build(ctx, ix, opts, B));
+    const int64_t nb = B.nb;
+    const int4* rec = B.rec;
+    const DqIndex v = B.v;
     // 3. the probes, P per workgroup
     const int P = depth_hist_tile(D, depth_hist_budget());
     const size_t lds = (size_t)P * (size_t)(D + 1) * 8;

@@ -34,6 +34,7 @@
 #include "depth_profile.hip.h"
 #include "depth_query.hip.h"
 #include "depth_hist.hip.h"
+#include "depth_quant.hip.h"
 #include "setop.hip.h"
 #include "multi.hip.h"
 #include "pairwise.hip.h"
@@ -59,6 +60,7 @@ using namespace ivj;
 #include "host_depth_profile.hip.h"
 #include "host_depth_query.hip.h"
 #include "host_depth_hist.hip.h"
+#include "host_depth_quant.hip.h"
 #include "host_setop.hip.h"
 #include "host_multi.hip.h"
 #include "host_pairwise.hip.h"
@@ -1015,6 +1017,50 @@ int ivj_depth_hist_contigs(ivj_ctx* ctx, const ivj_side* frame, const ivj_opts* 
     IVJ_TRY(depth_hist_contigs_dev(ctx, h.ix, opts, max_depth, (int64_t*)out.p));
     HostXfer copy(ctx->stream, &ctx->xfer);
     copy.d2h(hist, out.p, bytes);
+    HIP_TRY(copy.finish());
+    return IVJ_OK;
+} IVJ_ABI_CATCH
+
+// ---------------------------------------------------------------- depth quantiles (order statistics of the depth, per row)
+
+int ivj_depth_quantiles_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, const ivj_opts* opts, int32_t n_ranks,
+                            const int64_t* ranks_dev, int32_t* out_dev) try {
+    if (!ctx || !ix) return fail(IVJ_EINVAL, "ctx or index is NULL");
+    IVJ_TRY(check_opts(opts));
+    IVJ_TRY(check_side(probe_dev, "probe"));
+    IVJ_TRY(depth_quant_check(n_ranks, ranks_dev, out_dev));
+    DeviceGuard g(ctx->device);
+    return depth_quant_dev(ctx, ix, probe_dev, opts, n_ranks, ranks_dev, out_dev);
+} IVJ_ABI_CATCH
+
+int ivj_depth_quantiles(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, int32_t n_ranks, const int64_t* ranks,
+                        int32_t* out) try {
+    if (!ctx) return fail(IVJ_EINVAL, "ctx is NULL");
+    IVJ_TRY(check_opts(opts));
+    IVJ_TRY(check_side(probe, "probe"));
+    IVJ_TRY(check_side(build, "build"));
+    IVJ_TRY(depth_quant_check(n_ranks, ranks, out));
+    if (probe->n == 0) return IVJ_OK;
+    DeviceGuard g(ctx->device);
+    DevSide dp, db;
+    IVJ_TRY(upload_side(ctx, build, db));
+    IVJ_TRY(upload_side(ctx, probe, dp));
+    IndexHolder h;
+    IVJ_TRY(index_build(ctx, &db.s, opts, 3, &h.ix));      // sweep only (no lookup tables) + the end order: what depth_core reads
+    const size_t cells = (size_t)probe->n * (size_t)n_ranks;
+    DevBuf buf;                                            // the ranks, then the answers
+    const hipError_t e = hipMalloc(&buf.p, cells * 12);
+    if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(depth quantiles): ") + hipGetErrorString(e));
+    int64_t* d_ranks = (int64_t*)buf.p;
+    int32_t* d_out = (int32_t*)(d_ranks + cells);
+    {
+        HostXfer copy(ctx->stream, &ctx->xfer);
+        copy.h2d(d_ranks, ranks, cells * 8);
+        HIP_TRY(copy.finish());
+    }
+    IVJ_TRY(depth_quant_dev(ctx, h.ix, &dp.s, opts, n_ranks, d_ranks, d_out));
+    HostXfer copy(ctx->stream, &ctx->xfer);
+    copy.d2h(out, d_out, cells * 4);
     HIP_TRY(copy.finish());
     return IVJ_OK;
 } IVJ_ABI_CATCH

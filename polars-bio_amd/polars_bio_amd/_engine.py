@@ -40,6 +40,7 @@ ABI_SYMBOLS = [
     "ivj_overlap_bases", "ivj_overlap_bases_dev", "ivj_depth_profile", "ivj_depth_profile_dev",
     "ivj_depth", "ivj_blocks_free", "ivj_depth_dev", "ivj_depth_summary", "ivj_depth_summary_dev",
     "ivj_depth_hist", "ivj_depth_hist_contigs", "ivj_depth_hist_dev", "ivj_depth_hist_contigs_dev",
+    "ivj_depth_quantiles", "ivj_depth_quantiles_dev",
     "ivj_setop", "ivj_regions_free", "ivj_set_stats", "ivj_setop_dev", "ivj_set_stats_dev",
     "ivj_multi_inter", "ivj_segments_free", "ivj_multi_inter_dev", "ivj_multi_pairwise", "ivj_multi_pairwise_dev",
     "ivj_stream_open", "ivj_stream_submit", "ivj_stream_flush", "ivj_stream_set_nearest_ignore", "ivj_stream_close",
@@ -66,6 +67,15 @@ HIST_LDS_BYTES, HIST_MAX_TILE = 65536, 512      # include/ivjoin.h: IVJ_HIST_LDS
 def depth_hist_tile(max_depth: int) -> int:
     """probe rows one workgroup of ivj_depth_hist owns (include/ivjoin.h); informative: the result does not depend on it"""
     return min(max(HIST_LDS_BYTES // ((int(max_depth) + 1) * 8), 1), HIST_MAX_TILE)
+
+
+MAX_QUANT_RANKS = 16                 # include/ivjoin.h: IVJ_MAX_QUANT_RANKS, ivj_depth_quantiles accepts 1 .. this many ranks per row
+QUANT_BITS, QUANT_LDS_BYTES, QUANT_MAX_TILE = 4, 65536, 512      # include/ivjoin.h: IVJ_QUANT_BITS, IVJ_QUANT_LDS_BYTES, IVJ_QUANT_MAX_TILE
+
+
+def depth_quant_tile(n_ranks: int) -> int:
+    """probe rows one workgroup of ivj_depth_quantiles owns (include/ivjoin.h); informative: the result does not depend on it"""
+    return min(max(QUANT_LDS_BYTES // (int(n_ranks) * (1 << QUANT_BITS) * 8), 1), QUANT_MAX_TILE)
 
 # the operations of ivj_setop / ivj_setop_dev (include/ivjoin.h: IVJ_SETOP_*)
 SETOP_INTERSECTION, SETOP_UNION, SETOP_DIFFERENCE, SETOP_SYMMETRIC_DIFFERENCE = 0, 1, 2, 3
@@ -313,6 +323,8 @@ def load_library() -> C.CDLL:
         L.ivj_depth_hist_contigs.argtypes = [vp, P, O, C.c_int32, vp]
         L.ivj_depth_hist_dev.argtypes = [vp, vp, P, O, C.c_int32, vp]
         L.ivj_depth_hist_contigs_dev.argtypes = [vp, vp, O, C.c_int32, vp]
+        L.ivj_depth_quantiles.argtypes = [vp, P, P, O, C.c_int32, vp, vp]
+        L.ivj_depth_quantiles_dev.argtypes = [vp, vp, P, O, C.c_int32, vp, vp]
         L.ivj_stream_open.argtypes = [vp, P, O, C.c_int, C.c_int64, C.POINTER(vp)]
         L.ivj_stream_submit.argtypes = [vp, P, C.POINTER(_StreamResult)]
         L.ivj_stream_flush.argtypes = [vp, C.POINTER(_StreamResult)]
@@ -1000,6 +1012,26 @@ class Engine:
         del keep_f
         return hist
 
+    def depth_quantiles(self, probe, build, strict: bool, n_contigs: int, ranks, partition_mode: int = 0) -> np.ndarray:
+        """pb.depth_quantiles: ranks int64 (n, K), 0-based, K in 1 .. MAX_QUANT_RANKS -> int32 (n, K), probe order: cell (i, j) =
+        the ranks[i, j]-th smallest depth of the build side over the positions of probe row i (uncovered positions count at
+        depth 0); -1 for a rank outside [0, positions of the row) and for a row without a position or outside the dictionary."""
+        ps, keep_p = _host_side(*probe)
+        bs, keep_b = _host_side(*build)
+        o = make_opts(strict, n_contigs, partition_mode=partition_mode)
+        ranks = np.ascontiguousarray(ranks, dtype=np.int64)
+        if ranks.ndim != 2 or ranks.shape[0] != ps.n:
+            raise ValueError(f"ranks must be an (n, K) matrix with one row per probe row, got shape {ranks.shape} for {ps.n} rows")
+        k = ranks.shape[1]
+        out = np.empty((ps.n, k), np.int32)
+        # (an array without elements still has to pass a non-NULL address: the entry checks its pointers before the row count)
+        keep_r = ranks if ranks.size else np.zeros(1, np.int64)
+        keep_o = out if out.size else np.empty(1, np.int32)
+        _check(self.L, self.L.ivj_depth_quantiles(self.h, C.byref(ps), C.byref(bs), C.byref(o), k, keep_r.ctypes.data, keep_o.ctypes.data),
+               "ivj_depth_quantiles")
+        del keep_p, keep_b
+        return out
+
     def _pieces(self, fn, name, a, b, strict, n_contigs, partition_mode=0):
         sa, keep_a = _host_side(*a)
         sb, keep_b = _host_side(*b)
@@ -1501,6 +1533,11 @@ class Engine:
         """hist_ptr: device address (0 = NULL) of row-major int64[n_contigs, max_depth + 1]."""
         _check(self.L, self.L.ivj_depth_hist_contigs_dev(self.h, ix.handle, C.byref(opts), int(max_depth), C.c_void_p(hist_ptr or None)),
                "ivj_depth_hist_contigs_dev")
+
+    def depth_quantiles_dev(self, ix: DeviceIndex, probe: _Side, opts: _Opts, n_ranks: int, ranks_ptr: int, out_ptr: int):
+        """ranks_ptr / out_ptr: device addresses (0 = NULL) of row-major int64[n, n_ranks] and int32[n, n_ranks]."""
+        _check(self.L, self.L.ivj_depth_quantiles_dev(self.h, ix.handle, C.byref(probe), C.byref(opts), int(n_ranks), C.c_void_p(ranks_ptr or None),
+                                                       C.c_void_p(out_ptr or None)), "ivj_depth_quantiles_dev")
 
     def permute_overlaps_dev(self, ix: DeviceIndex, probe: _Side, opts: _Opts, contig_len_ptr: int, offsets_ptr: int, n_perm: int,
                              n_pairs_ptr: int, n_rows_ptr: int):

@@ -491,6 +491,33 @@ class DeviceJoin:
                 ix.close()
         return hist
 
+    def depth_quantiles(self, probe: DeviceSide, build: DeviceSide, strict: bool, n_contigs: int, ranks, index=None, out=None,
+                        partition_mode: int = 0):
+        """Per probe row and per rank the order statistic of the build side's depth over the row's positions: ``ranks`` is a
+        contiguous int64 tensor (probe.n, K) in HBM, 0-based, K in 1 .. 16 -> int32 tensor (probe.n, K) in HBM; -1 for a rank
+        outside the row's positions and for a row without a position.  ``index``: a prebuilt index of the build side (any form);
+        ``out``: a contiguous int32 tensor of that shape."""
+        torch = self.torch
+        opts = make_opts(strict, n_contigs, partition_mode=partition_mode)
+        if ranks.dtype != torch.int64 or ranks.dim() != 2 or ranks.shape[0] != probe.n or not ranks.is_contiguous():
+            raise ValueError("ranks must be a contiguous int64 tensor of shape (probe.n, K)")
+        k = int(ranks.shape[1])
+        if out is not None and (out.dtype != torch.int32 or tuple(out.shape) != (probe.n, k) or not out.is_contiguous()):
+            raise ValueError("out must be a contiguous int32 tensor of shape (probe.n, K)")
+        own = index is None
+        ix = self.engine.index_build_dev(build.as_c(), opts, True, sweep_only=True) if own else index
+        try:
+            dev = probe.start.device
+            res = out if out is not None else torch.empty((probe.n, k), dtype=torch.int32, device=dev)
+            # (a tensor without elements has no address, and the entry refuses a NULL pointer whatever the row count)
+            spare_r = ranks if ranks.numel() else torch.zeros(1, dtype=torch.int64, device=dev)
+            spare_o = res if res.numel() else torch.empty(1, dtype=torch.int32, device=dev)
+            self.engine.depth_quantiles_dev(ix, probe.as_c(), opts, k, spare_r.data_ptr(), spare_o.data_ptr())
+        finally:
+            if own:
+                ix.close()
+        return res
+
     def depth_histogram_contigs(self, frame: DeviceSide, strict: bool, n_contigs: int, max_depth: int, index=None, out=None):
         """Per contig the number of positions at each depth 1 .. max_depth of the frame (the last bin: max_depth or more; bin 0 is
         0, the engine does not know a contig's length) -> int64 tensor (n_contigs, max_depth + 1) in HBM.  ``index`` / ``out`` as

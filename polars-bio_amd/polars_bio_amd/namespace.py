@@ -15,6 +15,7 @@ _ALIASES = {
     "overlap": (range_op.overlap, True), "nearest": (range_op.nearest, True), "count_overlaps": (range_op.count_overlaps, True),
     "coverage": (range_op.coverage, True), "mean_depth": (range_op.mean_depth, True), "depth_summary": (range_op.depth_summary, True),
     "depth_profile": (range_op.depth_profile, True), "depth_histogram": (range_op.depth_histogram, True),
+    "depth_quantiles": (range_op.depth_quantiles, True), "median_depth": (range_op.median_depth, True),
     "subtract": (range_op.subtract, True), "map_overlaps": (range_op.map_overlaps, True),
     "signal_summary": (range_op.signal_summary, True), "signal_profile": (range_op.signal_profile, True),
     "permutation_test": (range_op.permutation_test, True),

@@ -27,7 +27,7 @@ from .constants import DEFAULT_INTERVAL_COLUMNS
 
 logger = logging.getLogger("polars_bio_amd")
 
-__all__ = ["overlap", "overlap_batches", "count_overlaps_batches", "nearest_batches", "nearest", "count_overlaps", "coverage", "mean_depth", "depth_profile", "depth_summary", "depth_histogram", "genome_depth_histogram", "merge", "cluster", "complement", "subtract", "map_overlaps", "signal_summary", "signal_profile",
+__all__ = ["overlap", "overlap_batches", "count_overlaps_batches", "nearest_batches", "nearest", "count_overlaps", "coverage", "mean_depth", "depth_profile", "depth_summary", "depth_histogram", "genome_depth_histogram", "depth_quantiles", "median_depth", "quantile_ranks", "merge", "cluster", "complement", "subtract", "map_overlaps", "signal_summary", "signal_profile",
            "set_intersect", "set_union", "set_difference", "set_symmetric_difference", "jaccard", "multi_intersect", "consensus", "pairwise_jaccard",
            "FilterOp", "RangeOp", "OverlapOutputMode"]
 
@@ -1010,7 +1010,8 @@ def depth_summary(
     order kept.  ``thresholds``: an iterable of at most 8 distinct ints >= 1; empty gives ``max_depth`` only.  0-based frames
     are half-open (intervals that only touch share nothing), 1-based frames closed.  Rows of either frame that cover no
     position, and rows with a null chrom, share nothing (such df1 rows get 0 in every column).
-    ``on_cols``: only df2 intervals of the df1 row's group of equal (chrom, on values) count; a null on-value matches nothing."""
+    ``on_cols``: only df2 intervals of the df1 row's group of equal (chrom, on values) count; a null on-value matches nothing.
+    More than 8 thresholds: ``pb.depth_histogram``; quantiles: ``pb.depth_quantiles``."""
     on_cols = _validate_overlap_input(cols1, cols2, on_cols, suffixes, output_type)
     thresholds = _validate_thresholds(thresholds)
     _check_on_cols_present(on_cols, df1, df2)
@@ -1067,7 +1068,8 @@ def depth_histogram(
     chrom, share nothing (such df1 rows get zeros).  ``on_cols``: only df2 intervals of the df1 row's group of equal (chrom, on
     values) count; a null on-value matches nothing.
 
-    Eager, one device.  Not covered: streaming inputs or outputs, a weighted (signal) histogram, quantiles."""
+    Eager, one device.  Quantiles: ``pb.depth_quantiles``.  Not covered: streaming inputs or outputs, a weighted (signal)
+    histogram."""
     on_cols = _validate_overlap_input(cols1, cols2, on_cols, suffixes, "pyarrow.Table" if output_type == "numpy.ndarray" else output_type)
     max_depth = _validate_max_depth(max_depth)
     if output not in ("bases", "fraction"):
@@ -1091,6 +1093,141 @@ def depth_histogram(
         values = pa.array(frac.reshape(-1), type=pa.float64(), mask=np.repeat(none, max_depth + 1))
     t = t1.append_column("histogram", pa.FixedSizeListArray.from_arrays(values, max_depth + 1))
     return _finish_eager(t, output_type, zero_based, None)
+
+
+def quantile_ranks(length, q):
+    """The order statistics a quantile of a list of ``length`` sorted values rests on, with numpy's convention: h = q (L - 1)
+    evaluated in IEEE float64 -> (lo = floor(h), hi = ceil(h), both int64, g = h - lo float64).  ``length``: int64 lengths (any
+    shape), ``q``: a float in [0, 1] or an array that broadcasts against the lengths.  A length <= 0 has no order statistic: lo =
+    hi = -1, g = 0.  Pure host arithmetic, vectorised; L - 1 < 2^53 is exact in float64, so h is the correctly rounded product."""
+    length = np.asarray(length, dtype=np.int64)
+    qf = np.asarray(q, dtype=np.float64)
+    if qf.size and not ((qf >= 0.0) & (qf <= 1.0)).all():
+        raise ValueError(f"a quantile must lie in [0, 1], got {q!r}")
+    length, qf = np.broadcast_arrays(length, qf)
+    ok = length > 0
+    h = qf * np.where(ok, length - 1, 0).astype(np.float64)
+    lo_f = np.floor(h)
+    lo = np.where(ok, lo_f.astype(np.int64), -1)
+    hi = np.where(ok, np.ceil(h).astype(np.int64), -1)
+    g = np.where(ok, h - lo_f, 0.0)
+    assert (hi[ok] < length[ok]).all() and (lo[ok] >= 0).all() and (hi - lo <= 1).all()
+    return lo, hi, g
+
+
+QUANTILE_METHODS = ("lower", "higher", "midpoint", "linear")
+MAX_QUANTILES = 8
+
+
+def _validate_quantiles(q, method) -> list:
+    if method not in QUANTILE_METHODS:
+        raise ValueError(f"method must be one of {', '.join(map(repr, QUANTILE_METHODS))}, got {method!r}")
+    if isinstance(q, (int, float, np.integer, np.floating)) and not isinstance(q, (bool, np.bool_)):
+        q = (q,)
+    try:
+        qs = [float(x) for x in q]
+    except (TypeError, ValueError):
+        raise ValueError(f"q must be a float or an iterable of floats in [0, 1], got {q!r}") from None
+    if not 1 <= len(qs) <= MAX_QUANTILES:
+        raise ValueError(f"between 1 and {MAX_QUANTILES} quantiles per call, got {len(qs)}")
+    for x in qs:
+        if not 0.0 <= x <= 1.0:                            # (a NaN fails both comparisons)
+            raise ValueError(f"a quantile must lie in [0, 1], got {x!r}")
+    if len(set(qs)) != len(qs):
+        raise ValueError(f"the quantiles must be distinct, got {qs!r}")
+    return qs
+
+
+def _quantile_engine(what: str):
+    eng = default_engine()
+    if not hasattr(eng, "depth_quantiles"):
+        raise NotImplementedError(f"{what} needs a single-device engine; the default engine is a {type(eng).__name__} "
+                                  "(several devices), which has no quantile kernel")
+    return eng
+
+
+def _depth_quantile_matrix(what, df1, df2, qs, method, suffixes, on_cols, cols1, cols2, output_type):
+    """-> (t1, zero_based, values (n, len(qs)) int64 or float64, null bool[n])"""
+    on_cols = _validate_overlap_input(cols1, cols2, on_cols, suffixes, "pyarrow.Table" if output_type == "numpy.ndarray" else output_type)
+    _check_on_cols_present(on_cols, df1, df2)
+    zero_based = validate_coordinate_systems(df1, df2)
+    t1, t2, probe, build, n_contigs, _keys = _prepare(df1, df2, cols1, cols2, on_cols)
+    lo, hi, g = quantile_ranks(_side_lengths(probe, zero_based)[:, None], np.asarray(qs, np.float64)[None, :])
+    if method in ("lower", "higher"):
+        ranks = lo if method == "lower" else hi
+    else:                                                  # lo and hi of each quantile side by side
+        ranks = np.stack([lo, hi], axis=2).reshape(len(lo), 2 * len(qs))
+    v = _quantile_engine(what).depth_quantiles(probe, build, strict=zero_based, n_contigs=n_contigs, ranks=ranks).astype(np.int64)
+    null = (v < 0).any(axis=1)                             # a row without a position, or outside the dictionary (null chrom)
+    if method in ("lower", "higher"):
+        return t1, zero_based, v, null
+    vlo, vhi = v[:, 0::2].astype(np.float64), v[:, 1::2].astype(np.float64)
+    val = (vlo + vhi) / 2.0 if method == "midpoint" else vlo + (vhi - vlo) * g
+    return t1, zero_based, np.where(null[:, None], np.nan, val), null
+
+
+def depth_quantiles(
+    df1,
+    df2,
+    q=(0.25, 0.5, 0.75),
+    method: str = "lower",
+    suffixes: tuple = ("_1", "_2"),
+    on_cols: Union[list, None] = None,
+    cols1: Union[list, None] = ["chrom", "start", "end"],
+    cols2: Union[list, None] = ["chrom", "start", "end"],
+    output_type: str = "polars.LazyFrame",
+):
+    """Exact quantiles of df2's depth over the positions of every df1 interval: the median depth of a region and its quartiles
+    (mosdepth ``--use-median``; what a CNV / target-QC normaliser divides by), without a histogram leaving the device and for any
+    depth up to 2^31 - 1.
+
+    For a df1 row with L >= 1 positions let v[0] <= ... <= v[L - 1] be the depths of its positions, sorted: the number of df2
+    intervals of its contig that cover the position, 0 for an uncovered one.  For a quantile q in [0, 1]: h = q (L - 1) in float64,
+    lo = floor(h), hi = ceil(h), g = h - lo (``quantile_ranks``), and ``method``, with numpy's names, selects
+    ``"lower"`` (default) v[lo] | ``"higher"`` v[hi] (both Int64) | ``"midpoint"`` (v[lo] + v[hi]) / 2 | ``"linear"``
+    v[lo] + (v[hi] - v[lo]) g (both Float64).  The device answers the order statistics; the quantile is host arithmetic on them.
+
+    Output = df1 columns + one column per quantile, ``depth_q<q>`` with q as ``repr(float(q))`` (``depth_q0.5``), in the given
+    order, df1 row order kept.  ``q``: 1 .. 8 distinct values in [0, 1], else ``ValueError``.  Rows without a position (empty,
+    inverted, null chrom or null on-value) get null.  ``output_type="numpy.ndarray"`` returns the bare (n, len(q)) matrix: int64
+    with -1 for null (``"lower"``, ``"higher"``), float64 with NaN for null (``"midpoint"``, ``"linear"``).
+    0-based frames are half-open, 1-based frames closed.  ``on_cols``: only df2 intervals of the df1 row's group of equal
+    (chrom, on values) count.  Identities: q = 1 gives ``depth_summary``'s ``max_depth``; q = 0 is positive exactly where
+    ``pb.coverage`` equals the row's length.
+
+    Eager, one device (a several-device engine raises ``NotImplementedError``).  Not covered: streaming inputs or outputs,
+    several devices, a weighted (signal) quantile, per-contig / genome-wide quantiles, more than 8 quantiles per call."""
+    qs = _validate_quantiles(q, method)
+    t1, zero_based, val, null = _depth_quantile_matrix("depth_quantiles", df1, df2, qs, method, suffixes, on_cols, cols1, cols2, output_type)
+    if output_type == "numpy.ndarray":
+        return np.where(null[:, None], -1, val) if val.dtype == np.int64 else val
+    typ = pa.int64() if val.dtype == np.int64 else pa.float64()
+    for k, x in enumerate(qs):
+        t1 = t1.append_column(f"depth_q{x!r}", pa.array(np.ascontiguousarray(val[:, k]), type=typ, mask=null))
+    return _finish_eager(t1, output_type, zero_based, None)
+
+
+def median_depth(
+    df1,
+    df2,
+    suffixes: tuple = ("_1", "_2"),
+    on_cols: Union[list, None] = None,
+    cols1: Union[list, None] = ["chrom", "start", "end"],
+    cols2: Union[list, None] = ["chrom", "start", "end"],
+    output_type: str = "polars.LazyFrame",
+):
+    """The median depth of df2 over every df1 interval: ``depth_quantiles`` with ``q = 0.5`` and ``method="lower"`` (the value at
+    rank floor((L - 1) / 2) of the row's L sorted per-position depths, uncovered positions at 0), as one Int64 column
+    ``median_depth``; null for a row without a position.  The robust counterpart of ``pb.mean_depth``, which one PCR pile-up
+    ruins.  ``output_type="numpy.ndarray"``: the bare (n, 1) int64 matrix, -1 for null.
+
+    Eager, one device.  Not covered: streaming inputs or outputs, several devices, a weighted (signal) median, a per-contig /
+    genome-wide median."""
+    t1, zero_based, val, null = _depth_quantile_matrix("median_depth", df1, df2, [0.5], "lower", suffixes, on_cols, cols1, cols2, output_type)
+    if output_type == "numpy.ndarray":
+        return np.where(null[:, None], -1, val)
+    t1 = t1.append_column("median_depth", pa.array(np.ascontiguousarray(val[:, 0]), type=pa.int64(), mask=null))
+    return _finish_eager(t1, output_type, zero_based, None)
 
 
 def genome_depth_histogram(
