@@ -277,6 +277,54 @@ int ivj_overlap_thresh_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_de
 int ivj_count_overlaps_thresh_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, const ivj_opts* opts, const ivj_thresholds* thr_dev,
                                   int64_t* counts_dev);
 
+/* ---- distance window: pb.window / pb.count_window -- every build row within a distance of every probe row ------------------------
+ * (bedtools window -w / -l / -r / -sw, pyranges join(slack=), bioframe pair_by_distance).  The distance is that of ivj_nearest,
+ * evaluated in 64 bits.  For a probe (df1) row a and a build (df2) row b of one contig (one group, when the contig column carries
+ * group ids), with (<) = < for IVJ_FILTER_STRICT (0-based half-open) and <= for IVJ_FILTER_WEAK (1-based closed):
+ *   gap_right = b.start - a.end      (b lies after a:  !(b.start (<) a.end))
+ *   gap_left  = a.start - b.end      (b lies before a: !(a.start (<) b.end))
+ *   d(a, b)   = 0 if the rows overlap (b.start (<) a.end && a.start (<) b.end), else max(gap_right, gap_left)
+ * Bookended half-open rows do not overlap and have d = 0; adjacent closed rows have d = 1.  Every probe row has a left extent L(a)
+ * and a right extent R(a), both in [0, 2^32 - 1]: `left` / `right` for all rows, or -- per pointer, when non-NULL -- probe_left[i] /
+ * probe_right[i], indexed by the row's position in the probe columns (not by row_id).  A pair is kept iff ALL of
+ *   - both rows cover at least one position (zero-length rows and rows with start > end never pair, on either side);
+ *   - d >= min_distance (with min_distance >= 1 overlapping rows drop out);
+ *   - the rows overlap, or b lies after a and d <= R(a), or b lies before a and d <= L(a) (a bookended pair, d = 0, counts on the
+ *     side it lies on).
+ * Rows with a contig id outside [0, n_contigs) (a null chrom or on-value) never pair.  min_distance above both extents is legal
+ * and gives the empty result.  On half-open frames `bedtools window -w W` is left = right = W - 1, on closed frames W.
+ * The signed distance of a pair is -d when b lies before a in coordinates, d otherwise (0 on overlap); |d| <= 2^32 - 1: int64.
+ * Order: the pairs of one probe row are contiguous and ordered by (build.start, build row); probe rows appear in input order, or
+ * bucket by bucket where the probe side was partitioned (ivj_opts.partition_mode, as ivj_overlap_thresh).  The output is identical
+ * from run to run.  The pointers of the struct live in the same memory space as the sides.  A NULL ivj_window is IVJ_EINVAL; a
+ * struct of zeros is valid (overlapping and touching pairs).  The streaming, Arrow-stream and multi-rank entries take no window.
+ * (New entries and a new struct change no existing struct or signature: IVJ_ABI_VERSION stays.) */
+typedef struct {
+    uint32_t left, right;              /* extents of every probe row ...                        */
+    const uint32_t* probe_left;        /* ... unless non-NULL: per probe row, by position       */
+    const uint32_t* probe_right;
+    uint32_t min_distance;             /* 0 = none */
+} ivj_window;
+
+/* Host path: the pairs as ivj_overlap returns them (library-owned, ivj_pairs_free); count, scan, then emit into exactly sized
+ * buffers.  dist (NULL = not wanted): *dist receives a library-owned column of out->n_pairs signed distances (NULL when there is
+ * no pair); free it with ivj_window_dist_free. */
+int ivj_overlap_window(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, const ivj_window* win,
+                       ivj_pairs* out, int64_t** dist);
+void ivj_window_dist_free(int64_t* dist);
+/* counts[i] = the kept pairs of probe row i, probe order kept; caller buffer of probe->n. */
+int ivj_count_window(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, const ivj_window* win,
+                     int64_t* counts);
+/* Device path on an index of ivj_index_build_dev (any with_end_order but the sweep-only form).  The capacity contract of
+ * ivj_overlap_thresh_dev: *n_pairs always receives the total; IVJ_ECAPACITY when it exceeds `capacity`, and nothing is written then.
+ * NULL buffers with capacity 0 = count only (IVJ_OK).  dist_dev (NULL = not wanted): `capacity` int64.  Candidate ranges of any
+ * length are handled here.  Blocks until the total is known (one 8-byte D2H). */
+int ivj_overlap_window_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, const ivj_opts* opts, const ivj_window* win_dev,
+                           int32_t* probe_idx_dev, int32_t* build_idx_dev, int64_t* dist_dev, int64_t capacity, int64_t* n_pairs);
+/* Per-probe counts only (no pair is enumerated to HBM); enqueued on the context's stream. */
+int ivj_count_window_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, const ivj_opts* opts, const ivj_window* win_dev,
+                         int64_t* counts_dev);
+
 /* ---- join kinds of pb.overlap other than inner: semi, anti, left outer (bedtools intersect -u / -v / -loj) -------------------------
  * "The predicate" is the plain overlap predicate of ivj_overlap, or -- with a non-NULL ivj_thresholds -- the thresholded one of the
  * section above.  With cnt[i] = what ivj_count_overlaps (ivj_count_overlaps_thresh) returns for probe row i under the very same

@@ -39,6 +39,7 @@
 #include "multi.hip.h"
 #include "pairwise.hip.h"
 #include "thresh.hip.h"
+#include "window.hip.h"
 #include "select.hip.h"
 #include "merge_agg.hip.h"
 #include "overlap_agg.hip.h"
@@ -65,6 +66,7 @@ using namespace ivj;
 #include "host_multi.hip.h"
 #include "host_pairwise.hip.h"
 #include "host_thresh.hip.h"
+#include "host_window.hip.h"
 #include "host_select.hip.h"
 #include "host_overlap_agg.hip.h"
 #include "host_signal.hip.h"
@@ -1540,6 +1542,96 @@ int ivj_count_overlaps_thresh(ivj_ctx* ctx, const ivj_side* probe, const ivj_sid
     if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(counts): ") + hipGetErrorString(e));
     ThreshPlan plan;
     IVJ_TRY(thresh_count(ctx, H.h.ix, &H.dp.s, opts, &H.dthr, (int64_t*)dc.p, false, plan, nullptr));
+    HostXfer copy(ctx->stream, &ctx->xfer);
+    copy.d2h(counts, dc.p, (size_t)probe->n * 8);
+    HIP_TRY(copy.finish());
+    return IVJ_OK;
+} IVJ_ABI_CATCH
+
+// ---------------------------------------------------------------- distance window (window.hip.h, host_window.hip.h)
+
+int ivj_overlap_window_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, const ivj_opts* opts, const ivj_window* win_dev,
+                           int32_t* probe_idx_dev, int32_t* build_idx_dev, int64_t* dist_dev, int64_t capacity, int64_t* n_pairs) try {
+    if (!ctx || !ix || !n_pairs) return fail(IVJ_EINVAL, "ctx, index or n_pairs is NULL");
+    IVJ_TRY(check_opts(opts));
+    IVJ_TRY(check_side(probe_dev, "probe"));
+    IVJ_TRY(check_window(win_dev));
+    if (capacity < 0 || (capacity > 0 && (!probe_idx_dev || !build_idx_dev))) return fail(IVJ_EINVAL, "bad output buffers");
+    DeviceGuard g(ctx->device);
+    return overlap_window_dev(ctx, ix, probe_dev, opts, win_dev, probe_idx_dev, build_idx_dev, dist_dev, capacity, n_pairs);
+} IVJ_ABI_CATCH
+
+int ivj_count_window_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, const ivj_opts* opts, const ivj_window* win_dev,
+                         int64_t* counts_dev) try {
+    if (!ctx || !ix) return fail(IVJ_EINVAL, "ctx or index is NULL");
+    IVJ_TRY(check_opts(opts));
+    IVJ_TRY(check_side(probe_dev, "probe"));
+    IVJ_TRY(check_window(win_dev));
+    if (probe_dev->n > 0 && !counts_dev) return fail(IVJ_EINVAL, "counts is NULL");
+    DeviceGuard g(ctx->device);
+    WindowPlan plan;
+    return window_count(ctx, ix, probe_dev, opts, win_dev, counts_dev, false, plan, nullptr);
+} IVJ_ABI_CATCH
+
+void ivj_window_dist_free(int64_t* dist) { std::free(dist); }
+
+int ivj_overlap_window(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, const ivj_window* win,
+                       ivj_pairs* out, int64_t** dist) try {
+    if (!ctx || !out) return fail(IVJ_EINVAL, "ctx or out is NULL");
+    out->n_pairs = 0; out->probe_idx = nullptr; out->build_idx = nullptr;
+    if (dist) *dist = nullptr;
+    IVJ_TRY(check_opts(opts));
+    IVJ_TRY(check_side(probe, "probe"));
+    IVJ_TRY(check_side(build, "build"));
+    IVJ_TRY(check_window(win));
+    DeviceGuard g(ctx->device);
+    WindowHost H;
+    IVJ_TRY(window_upload(ctx, probe, build, opts, win, H));
+    WindowPlan plan;
+    int64_t total = 0;
+    IVJ_TRY(window_count(ctx, H.h.ix, &H.dp.s, opts, &H.dwin, nullptr, true, plan, &total));
+    if (total == 0) return IVJ_OK;
+    const size_t pair_bytes = dist ? 16 : 8;
+    if (!host_result_fits((size_t)total * pair_bytes))
+        return fail(IVJ_ENOMEM, "the result (" + std::to_string(total) + " pairs, " + std::to_string((size_t)total * pair_bytes >> 20) + " MiB) does not fit the available host memory; use ivj_overlap_window_dev");
+    DevBuf op, ob, od;
+    hipError_t e = hipMalloc(&op.p, (size_t)total * 4);
+    if (e == hipSuccess) e = hipMalloc(&ob.p, (size_t)total * 4);
+    if (e == hipSuccess && dist) e = hipMalloc(&od.p, (size_t)total * 8);
+    if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(pairs): ") + hipGetErrorString(e));
+    IVJ_TRY(window_emit(ctx, H.h.ix, plan, (int32_t*)op.p, (int32_t*)ob.p, (int64_t*)od.p));
+    auto drop = [&] { ivj_pairs_free(out); if (dist) { std::free(*dist); *dist = nullptr; } };
+    out->probe_idx = (int32_t*)host_result_alloc((size_t)total * 4);
+    out->build_idx = (int32_t*)host_result_alloc((size_t)total * 4);
+    if (dist) *dist = (int64_t*)host_result_alloc((size_t)total * 8);
+    if (!out->probe_idx || !out->build_idx || (dist && !*dist)) { drop(); return fail(IVJ_ENOMEM, "host malloc(pairs)"); }
+    HostXfer copy(ctx->stream, &ctx->xfer);
+    copy.d2h(out->probe_idx, op.p, (size_t)total * 4);
+    copy.d2h(out->build_idx, ob.p, (size_t)total * 4);
+    if (dist) copy.d2h(*dist, od.p, (size_t)total * 8);
+    const hipError_t ce = copy.finish();
+    if (ce != hipSuccess) { drop(); return fail(IVJ_EHIP, std::string("D2H(pairs): ") + hipGetErrorString(ce)); }
+    out->n_pairs = total;
+    return IVJ_OK;
+} IVJ_ABI_CATCH
+
+int ivj_count_window(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, const ivj_window* win,
+                     int64_t* counts) try {
+    if (!ctx) return fail(IVJ_EINVAL, "ctx is NULL");
+    IVJ_TRY(check_opts(opts));
+    IVJ_TRY(check_side(probe, "probe"));
+    IVJ_TRY(check_side(build, "build"));
+    IVJ_TRY(check_window(win));
+    if (probe->n == 0) return IVJ_OK;
+    if (!counts) return fail(IVJ_EINVAL, "counts is NULL");
+    DeviceGuard g(ctx->device);
+    WindowHost H;
+    IVJ_TRY(window_upload(ctx, probe, build, opts, win, H));
+    DevBuf dc;
+    hipError_t e = hipMalloc(&dc.p, (size_t)probe->n * 8);
+    if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(counts): ") + hipGetErrorString(e));
+    WindowPlan plan;
+    IVJ_TRY(window_count(ctx, H.h.ix, &H.dp.s, opts, &H.dwin, (int64_t*)dc.p, false, plan, nullptr));
     HostXfer copy(ctx->stream, &ctx->xfer);
     copy.d2h(counts, dc.p, (size_t)probe->n * 8);
     HIP_TRY(copy.finish());

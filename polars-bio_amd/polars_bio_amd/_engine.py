@@ -30,6 +30,7 @@ ABI_SYMBOLS = [
     "ivj_index_build_dev", "ivj_index_free", "ivj_overlap_count_dev", "ivj_overlap_fill_dev", "ivj_overlap_fused_dev",
     "ivj_count_overlaps_dev", "ivj_nearest_dev",
     "ivj_overlap_thresh", "ivj_count_overlaps_thresh", "ivj_overlap_thresh_dev", "ivj_count_overlaps_thresh_dev",
+    "ivj_overlap_window", "ivj_window_dist_free", "ivj_count_window", "ivj_overlap_window_dev", "ivj_count_window_dev",
     "ivj_overlap_select", "ivj_rowsel_free", "ivj_overlap_select_dev", "ivj_overlap_outer",
     "ivj_side_from_arrow", "ivj_materialize_dev", "ivj_overlap_fused_rows_dev", "ivj_take_dev", "ivj_take", "ivj_overlap_rows", "ivj_rows_free", "ivj_rows_export_arrow",
     "ivj_subtract", "ivj_complement", "ivj_pieces_free", "ivj_subtract_dev",
@@ -139,6 +140,11 @@ class _Opts(C.Structure):
 
 class _Thresholds(C.Structure):
     _fields_ = [("min_overlap", C.c_uint32), ("probe_min", C.c_void_p), ("build_min", C.c_void_p)]
+
+
+class _Window(C.Structure):
+    _fields_ = [("left", C.c_uint32), ("right", C.c_uint32), ("probe_left", C.c_void_p), ("probe_right", C.c_void_p),
+                ("min_distance", C.c_uint32)]
 
 
 class _RowSel(C.Structure):
@@ -257,6 +263,13 @@ def load_library() -> C.CDLL:
         L.ivj_count_overlaps_thresh.argtypes = [vp, P, P, O, T, vp]
         L.ivj_overlap_thresh_dev.argtypes = [vp, vp, P, O, T, vp, vp, C.c_int64, C.POINTER(C.c_int64)]
         L.ivj_count_overlaps_thresh_dev.argtypes = [vp, vp, P, O, T, vp]
+        W = C.POINTER(_Window)
+        L.ivj_overlap_window.argtypes = [vp, P, P, O, W, C.POINTER(_Pairs), C.POINTER(C.POINTER(C.c_int64))]
+        L.ivj_window_dist_free.argtypes = [C.POINTER(C.c_int64)]
+        L.ivj_window_dist_free.restype = None
+        L.ivj_count_window.argtypes = [vp, P, P, O, W, vp]
+        L.ivj_overlap_window_dev.argtypes = [vp, vp, P, O, W, vp, vp, vp, C.c_int64, C.POINTER(C.c_int64)]
+        L.ivj_count_window_dev.argtypes = [vp, vp, P, O, W, vp]
         L.ivj_overlap_select.argtypes = [vp, P, P, O, T, C.c_int32, C.POINTER(_RowSel)]
         L.ivj_rowsel_free.argtypes = [C.POINTER(_RowSel)]
         L.ivj_rowsel_free.restype = None
@@ -469,6 +482,18 @@ def make_thresholds(min_overlap: int = 0, probe_min_ptr: int = 0, build_min_ptr:
     return _Thresholds(int(min_overlap), probe_min_ptr or None, build_min_ptr or None)
 
 
+WINDOW_MAX = 0xFFFFFFFF     # ivj_window: extents and min_distance are uint32
+
+
+def make_window(left: int = 0, right: int = 0, probe_left_ptr: int = 0, probe_right_ptr: int = 0, min_distance: int = 0) -> _Window:
+    """ivj_window from the scalar extents, two (host or device) addresses of per-row uint32 extent columns (0 = the scalar holds) and
+    the minimum distance."""
+    for what, v in (("left", left), ("right", right), ("min_distance", min_distance)):
+        if not 0 <= int(v) <= WINDOW_MAX:
+            raise ValueError(f"{what} must fit uint32, got {v}")
+    return _Window(int(left), int(right), probe_left_ptr or None, probe_right_ptr or None, int(min_distance))
+
+
 def select_mode(mode) -> int:
     """"semi" / "anti" or SELECT_SEMI / SELECT_ANTI -> the IVJ_SELECT_* code (ValueError otherwise)."""
     if isinstance(mode, str):
@@ -540,6 +565,19 @@ class _LockedLib:
         call.__name__ = name
         setattr(self, name, call)
         return call
+
+
+class _DistOwner:
+    """Keeps the distance column of ivj_overlap_window alive for the numpy array that views it."""
+
+    def __init__(self, lib, ptr):
+        self.lib, self.ptr = lib, ptr
+
+    def __del__(self):
+        try:
+            self.lib.ivj_window_dist_free(self.ptr)
+        except Exception:
+            pass
 
 
 class _PairsOwner:
@@ -1102,6 +1140,50 @@ class Engine:
         del keep_p, keep_b, keep_t
         return counts
 
+    def _host_window(self, ps, left, right, probe_left, probe_right, min_distance):
+        pl, pr = _u32_min(probe_left, ps.n, "probe_left"), _u32_min(probe_right, ps.n, "probe_right")
+        w = make_window(left, right, pl.ctypes.data if pl is not None and ps.n else 0, pr.ctypes.data if pr is not None and ps.n else 0, min_distance)
+        return w, (pl, pr)
+
+    def overlap_window(self, probe, build, strict: bool, n_contigs: int, left: int = 0, right: int = 0, min_distance: int = 0,
+                       probe_left=None, probe_right=None, distance: bool = True, partition_mode: int = 0):
+        """pb.window (ivj_overlap_window): every build row within ``left`` bases before / ``right`` bases after each probe row (or the
+        row's entry of the uint32 columns ``probe_left`` / ``probe_right``) and at least ``min_distance`` away; the semantics are
+        those of include/ivjoin.h -> (probe_idx, build_idx, dist): dist the signed int64 distances (negative: the build row lies
+        before the probe row), or None with ``distance=False``."""
+        ps, keep_p = _host_side(*probe)
+        bs, keep_b = _host_side(*build)
+        w, keep_w = self._host_window(ps, left, right, probe_left, probe_right, min_distance)
+        o = make_opts(strict, n_contigs, partition_mode=partition_mode)
+        out = _Pairs()
+        dist = C.POINTER(C.c_int64)()
+        _check(self.L, self.L.ivj_overlap_window(self.h, C.byref(ps), C.byref(bs), C.byref(o), C.byref(w), C.byref(out),
+                                                 C.byref(dist) if distance else None), "ivj_overlap_window")
+        del keep_p, keep_b, keep_w
+        n = out.n_pairs
+        if n == 0:
+            self.L.ivj_pairs_free(C.byref(out))
+            return np.empty(0, np.int32), np.empty(0, np.int32), (np.empty(0, np.int64) if distance else None)
+        owner = _PairsOwner(load_library(), out)
+        d = None
+        if distance:
+            buf = (C.c_int64 * n).from_address(C.addressof(dist.contents))
+            buf._owner = _DistOwner(load_library(), dist)
+            d = np.frombuffer(buf, dtype=np.int64)
+        return _owned_view(out.probe_idx, n, owner), _owned_view(out.build_idx, n, owner), d
+
+    def count_window(self, probe, build, strict: bool, n_contigs: int, left: int = 0, right: int = 0, min_distance: int = 0,
+                     probe_left=None, probe_right=None, partition_mode: int = 0) -> np.ndarray:
+        """pb.count_window (ivj_count_window): the number of pairs ``overlap_window`` reports per probe row, int64, probe order kept."""
+        ps, keep_p = _host_side(*probe)
+        bs, keep_b = _host_side(*build)
+        w, keep_w = self._host_window(ps, left, right, probe_left, probe_right, min_distance)
+        o = make_opts(strict, n_contigs, partition_mode=partition_mode)
+        counts = np.zeros(ps.n, np.int64)
+        _check(self.L, self.L.ivj_count_window(self.h, C.byref(ps), C.byref(bs), C.byref(o), C.byref(w), counts.ctypes.data), "ivj_count_window")
+        del keep_p, keep_b, keep_w
+        return counts
+
     def permute_overlaps(self, probe, build, strict: bool, n_contigs: int, contig_len, offsets, partition_mode: int = 0):
         """pb.permutation_test (ivj_permute_overlaps): ``contig_len`` int32[n_contigs] (>= 1), ``offsets`` int32[n_perm, n_contigs]
         with 0 <= offsets[p, c] < contig_len[c].  -> (n_pairs int64[n_perm], n_rows int64[n_perm]): per permutation the matches
@@ -1321,6 +1403,23 @@ class Engine:
     def count_overlaps_thresh_dev(self, ix: DeviceIndex, probe: _Side, opts: _Opts, thr: _Thresholds, counts_ptr: int):
         _check(self.L, self.L.ivj_count_overlaps_thresh_dev(self.h, ix.handle, C.byref(probe), C.byref(opts), C.byref(thr),
                                                             C.c_void_p(counts_ptr)), "ivj_count_overlaps_thresh_dev")
+
+    def overlap_window_dev(self, ix: DeviceIndex, probe: _Side, opts: _Opts, win: _Window, probe_idx_ptr: int, build_idx_ptr: int, dist_ptr: int,
+                           capacity: int):
+        """Distance-window join on an index (ivj_overlap_window_dev; win from make_window with device addresses) -> (n_pairs, fits).
+        fits=False: nothing was written, grow the buffers to n_pairs.  Null buffers with capacity 0 count only; dist_ptr 0 = no
+        distance column."""
+        n = C.c_int64(0)
+        rc = self.L.ivj_overlap_window_dev(self.h, ix.handle, C.byref(probe), C.byref(opts), C.byref(win), C.c_void_p(probe_idx_ptr or None),
+                                           C.c_void_p(build_idx_ptr or None), C.c_void_p(dist_ptr or None), capacity, C.byref(n))
+        if rc == IVJ_ECAPACITY:
+            return n.value, False
+        _check(self.L, rc, "ivj_overlap_window_dev")
+        return n.value, True
+
+    def count_window_dev(self, ix: DeviceIndex, probe: _Side, opts: _Opts, win: _Window, counts_ptr: int):
+        _check(self.L, self.L.ivj_count_window_dev(self.h, ix.handle, C.byref(probe), C.byref(opts), C.byref(win), C.c_void_p(counts_ptr)),
+               "ivj_count_window_dev")
 
     def overlap_select_dev(self, ix: DeviceIndex, probe: _Side, opts: _Opts, thr: Optional[_Thresholds], mode: int, rows_ptr: int,
                            pad_ptr: int, capacity: int):

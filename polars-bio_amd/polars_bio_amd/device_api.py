@@ -16,7 +16,7 @@ import torch  # noqa: F401  (must precede the dlopen of libivjoin_hip.so in this
 from typing import Optional, Tuple
 
 from ._engine import (AGG_F64, AGG_I64, AGG_OPS, MULTI_CONSENSUS, MULTI_SEGMENTS, DeviceIndex, Engine, agg_ops_mask, check_multi, make_opts,
-                      make_thresholds, select_mode)
+                      make_thresholds, make_window, select_mode)
 
 
 class DeviceSide:
@@ -225,6 +225,79 @@ class DeviceJoin:
         ix = self.engine.index_build_dev(build.as_c(), opts, False) if own else index
         try:
             self.engine.count_overlaps_thresh_dev(ix, probe.as_c(), opts, thr, out.data_ptr())
+        finally:
+            if own:
+                ix.close()
+        return out
+
+    # ---- distance window (include/ivjoin.h: ivj_window) ----------------------------------------------
+    def _window(self, probe: DeviceSide, left: int, right: int, probe_left, probe_right, min_distance: int):
+        """probe_left / probe_right: contiguous CUDA tensors of one 4-byte unsigned extent per probe row (torch.uint32, or torch.int32
+        holding the same bits), or None for the scalar."""
+        torch = self.torch
+        for t, what in ((probe_left, "probe_left"), (probe_right, "probe_right")):
+            if t is None:
+                continue
+            if t.dtype not in (torch.int32, torch.uint32) or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (probe.n,):
+                raise ValueError(f"{what} must be a contiguous 4-byte integer CUDA tensor with one element per probe row")
+        return make_window(left, right, probe_left.data_ptr() if probe_left is not None and probe.n else 0,
+                           probe_right.data_ptr() if probe_right is not None and probe.n else 0, min_distance)
+
+    def overlap_window(self, probe: DeviceSide, build: DeviceSide, strict: bool, n_contigs: int, left: int = 0, right: int = 0,
+                       min_distance: int = 0, probe_left=None, probe_right=None, distance: bool = True, index=None, out=None,
+                       partition_mode: int = 0):
+        """Distance-window join (ivj_overlap_window_dev): every build row within ``left`` / ``right`` bases of each probe row and at
+        least ``min_distance`` away -> (probe_idx, build_idx, dist): int32, int32 and -- with ``distance`` -- the signed int64
+        distance (else None).  ``out``: optional preallocated CUDA tensors (int32, int32[, int64]), used when they hold the result
+        (views of their first n_pairs elements come back)."""
+        torch = self.torch
+        opts = make_opts(strict, n_contigs, partition_mode=partition_mode)
+        win = self._window(probe, left, right, probe_left, probe_right, min_distance)
+        dev = probe.start.device
+        if probe.n == 0 or build.n == 0:
+            e = torch.empty(0, dtype=torch.int32, device=dev)
+            return e, e.clone(), (torch.empty(0, dtype=torch.int64, device=dev) if distance else None)
+        own = index is None
+        ix = self.engine.index_build_dev(build.as_c(), opts, False) if own else index
+        try:
+            side = probe.as_c()
+            if out is not None:
+                if distance and len(out) < 3:
+                    raise ValueError("out must hold an int64 tensor for the distances")
+                cols = out[:3] if distance else out[:2]
+                total, fits = self.engine.overlap_window_dev(ix, side, opts, win, cols[0].data_ptr(), cols[1].data_ptr(),
+                                                             cols[2].data_ptr() if distance else 0, min(t.numel() for t in cols))
+                if fits:
+                    return cols[0][:total], cols[1][:total], (cols[2][:total] if distance else None)
+            else:
+                total, _ = self.engine.overlap_window_dev(ix, side, opts, win, 0, 0, 0, 0)
+            out_p = torch.empty(total, dtype=torch.int32, device=dev)
+            out_b = torch.empty(total, dtype=torch.int32, device=dev)
+            out_d = torch.empty(total, dtype=torch.int64, device=dev) if distance else None
+            if total:
+                self.engine.overlap_window_dev(ix, side, opts, win, out_p.data_ptr(), out_b.data_ptr(), out_d.data_ptr() if distance else 0, total)
+        finally:
+            if own:
+                ix.close()
+        return out_p, out_b, out_d
+
+    def count_window(self, probe: DeviceSide, build: DeviceSide, strict: bool, n_contigs: int, left: int = 0, right: int = 0,
+                     min_distance: int = 0, probe_left=None, probe_right=None, index=None, out=None, partition_mode: int = 0):
+        """Distance-window count (ivj_count_window_dev) -> int64 tensor, probe order kept (``out``: optional int64 CUDA tensor of
+        probe.n elements)."""
+        torch = self.torch
+        opts = make_opts(strict, n_contigs, partition_mode=partition_mode)
+        win = self._window(probe, left, right, probe_left, probe_right, min_distance)
+        if out is None:
+            out = torch.zeros(probe.n, dtype=torch.int64, device=probe.start.device)
+        elif out.dtype != torch.int64 or not out.is_cuda or not out.is_contiguous() or tuple(out.shape) != (probe.n,):
+            raise ValueError("out must be a contiguous int64 CUDA tensor with one element per probe row")
+        if probe.n == 0 or build.n == 0:
+            return out.zero_()
+        own = index is None
+        ix = self.engine.index_build_dev(build.as_c(), opts, False) if own else index
+        try:
+            self.engine.count_window_dev(ix, probe.as_c(), opts, win, out.data_ptr())
         finally:
             if own:
                 ix.close()

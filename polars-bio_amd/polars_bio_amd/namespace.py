@@ -13,6 +13,7 @@ from . import range_op
 # method -> (function, takes a second frame); "frames": takes a list of further frames, the call is made on [this frame, *others]
 _ALIASES = {
     "overlap": (range_op.overlap, True), "nearest": (range_op.nearest, True), "count_overlaps": (range_op.count_overlaps, True),
+    "window": (range_op.window, True), "count_window": (range_op.count_window, True),
     "coverage": (range_op.coverage, True), "mean_depth": (range_op.mean_depth, True), "depth_summary": (range_op.depth_summary, True),
     "depth_profile": (range_op.depth_profile, True), "depth_histogram": (range_op.depth_histogram, True),
     "depth_quantiles": (range_op.depth_quantiles, True), "median_depth": (range_op.median_depth, True),

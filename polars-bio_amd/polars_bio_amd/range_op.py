@@ -21,13 +21,13 @@ import pyarrow as pa
 import pyarrow.compute as pc
 
 from . import _arrow as A
-from ._engine import DEPTH_PROFILE_MAX_BINS, EngineError, default_engine
+from ._engine import DEPTH_PROFILE_MAX_BINS, WINDOW_MAX, EngineError, default_engine
 from ._metadata import validate_coordinate_system_single, validate_coordinate_systems
 from .constants import DEFAULT_INTERVAL_COLUMNS
 
 logger = logging.getLogger("polars_bio_amd")
 
-__all__ = ["overlap", "overlap_batches", "count_overlaps_batches", "nearest_batches", "nearest", "count_overlaps", "coverage", "mean_depth", "depth_profile", "depth_summary", "depth_histogram", "genome_depth_histogram", "depth_quantiles", "median_depth", "quantile_ranks", "merge", "cluster", "complement", "subtract", "map_overlaps", "signal_summary", "signal_profile",
+__all__ = ["overlap", "window", "count_window", "window_extents", "overlap_batches", "count_overlaps_batches", "nearest_batches", "nearest", "count_overlaps", "coverage", "mean_depth", "depth_profile", "depth_summary", "depth_histogram", "genome_depth_histogram", "depth_quantiles", "median_depth", "quantile_ranks", "merge", "cluster", "complement", "subtract", "map_overlaps", "signal_summary", "signal_profile",
            "set_intersect", "set_union", "set_difference", "set_symmetric_difference", "jaccard", "multi_intersect", "consensus", "pairwise_jaccard",
            "FilterOp", "RangeOp", "OverlapOutputMode"]
 
@@ -769,6 +769,146 @@ def count_overlaps(
     counts = default_engine().count_overlaps(probe, build, strict=zero_based, n_contigs=n_contigs)
     c1 = list(DEFAULT_INTERVAL_COLUMNS if cols1 is None else cols1)
     return A.from_arrow(_assemble_count(t1, counts, naive_query, c1, suffixes, on_cols), output_type, zero_based)
+
+
+# ---- distance window: pb.window / pb.count_window ------------------------------------------------------
+
+def _window_int(name, v) -> int:
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+        raise ValueError(f"{name} must be an int in [0, 2^32 - 1], got {v!r}")
+    if v < 0 or v > WINDOW_MAX:
+        raise ValueError(f"{name} must be in [0, 2^32 - 1], got {v}")
+    return int(v)
+
+
+def _validate_window(window, upstream, downstream, min_distance):
+    """-> (upstream, downstream, min_distance) as ints; ``upstream`` / ``downstream`` default to ``window``.  ValueError: a value
+    that is not an int (bools are refused), negative, or above 2^32 - 1."""
+    w = _window_int("window", window)
+    up = w if upstream is None else _window_int("upstream", upstream)
+    down = w if downstream is None else _window_int("downstream", downstream)
+    return up, down, _window_int("min_distance", min_distance)
+
+
+def window_extents(is_minus, upstream: int, downstream: int):
+    """The engine's extents of a call: -> (left, right, probe_left, probe_right).  Upstream of a "+" row is lower coordinates, so
+    left = upstream and right = downstream; a "-" row (``is_minus``: bool per df1 row, or None without a direction column) has
+    the two swapped.  Scalars when every row agrees (probe_left / probe_right are None then), else the two uint32 per-row columns
+    (the scalars are then 0 and not read)."""
+    if is_minus is None or upstream == downstream or not is_minus.any():
+        return upstream, downstream, None, None
+    if is_minus.all():
+        return downstream, upstream, None, None
+    up, down = np.uint32(upstream), np.uint32(downstream)
+    return 0, 0, np.where(is_minus, down, up).astype(np.uint32), np.where(is_minus, up, down).astype(np.uint32)
+
+
+def _window_setup(df1, df2, window, upstream, downstream, direction_col, min_distance, suffixes, on_cols, cols1, cols2, output_type):
+    up, down, md = _validate_window(window, upstream, downstream, min_distance)
+    on_cols = _validate_overlap_input(cols1, cols2, on_cols, suffixes, output_type)
+    _check_on_cols_present(on_cols, df1, df2)
+    if direction_col is not None:
+        if not isinstance(direction_col, str):
+            raise ValueError("direction_col must be the name of a df1 column")
+        names = _schema_names(df1)
+        if names is not None and direction_col not in names:
+            raise ValueError(f"direction_col '{direction_col}' not found in {names}")
+    zero_based = validate_coordinate_systems(df1, df2)
+    t1, t2, probe, build, n_contigs, keys = _prepare(df1, df2, cols1, cols2, on_cols)
+    is_minus = None
+    if direction_col is not None:
+        if direction_col not in t1.column_names:
+            raise ValueError(f"direction_col '{direction_col}' not found in {t1.column_names}")
+        is_minus = A.minus_rows(t1.column(direction_col))
+    left, right, pl, pr = window_extents(is_minus, up, down)
+    kw = dict(strict=zero_based, n_contigs=n_contigs, left=left, right=right, min_distance=md, probe_left=pl, probe_right=pr)
+    return zero_based, t1, t2, probe, build, keys, is_minus, kw
+
+
+def window(
+    df1,
+    df2,
+    window: int = 1000,
+    *,
+    upstream: Union[int, None] = None,
+    downstream: Union[int, None] = None,
+    direction_col: Union[str, None] = None,
+    min_distance: int = 0,
+    distance: bool = True,
+    signed_distance: bool = False,
+    suffixes: tuple = ("_1", "_2"),
+    on_cols: Union[list, None] = None,
+    cols1: Union[list, None] = ["chrom", "start", "end"],
+    cols2: Union[list, None] = ["chrom", "start", "end"],
+    output_type: str = "polars.LazyFrame",
+    limit: Union[int, None] = None,
+):
+    """Every df2 interval within a distance of every df1 interval, with the distance (bedtools ``window -w / -l / -r / -sw``,
+    pyranges ``join(slack=)``, bioframe ``pair_by_distance``): the join between ``overlap`` ("shares a position") and ``nearest``
+    ("the k closest").
+
+    The distance ``d`` is ``nearest``'s, evaluated in 64 bits: 0 when the two intervals overlap, else the gap between them
+    (``start2 - end1`` for a df2 interval after the df1 one, ``start1 - end2`` for one before it).  Bookended 0-based half-open
+    intervals do not overlap and have d = 0; adjacent 1-based closed intervals have d = 1.  A pair is kept iff both intervals
+    cover at least one position (zero-length rows and rows with start > end never pair), ``d >= min_distance`` (with
+    ``min_distance >= 1`` overlapping intervals drop out), and the df2 interval overlaps the df1 one, or lies downstream of it
+    with ``d <= downstream``, or upstream with ``d <= upstream``.  Rows with a null chrom or on-value never pair.
+    ``bedtools window -w W`` is ``window=W - 1`` on 0-based half-open frames and ``window=W`` on 1-based closed ones.
+
+    ``upstream`` / ``downstream`` default to ``window``; all three and ``min_distance`` are ints in [0, 2^32 - 1] (ValueError
+    otherwise).  Without ``direction_col`` upstream is the lower coordinates.  ``direction_col`` names a df1 column (usually the
+    strand; a column df1 lacks is a ValueError): a row whose value is the string "-" has upstream and downstream swapped, every
+    other value ("+", ".", null) reads as "+" -- ``nearest``'s rule and bedtools ``-sw``.  ``min_distance`` above both extents
+    is legal and gives the empty result.
+
+    Output: every df1 column + suffixes[0], every df2 column + suffixes[1], then ``distance`` (Int64; dropped with
+    ``distance=False``), one row per pair; the pairs of one df1 row are contiguous and ordered by (start, row) of the df2
+    interval.  ``signed_distance=True``: negative for a df2 interval upstream of the df1 row, read along the row's strand when
+    ``direction_col`` is set; otherwise the distance is non-negative.  ``on_cols``: pairs are formed within groups of equal
+    (chrom, on values) only.
+
+    The extents widen the candidate range of each df1 row on the device and the distance test runs there on every candidate;
+    the distances come back with the pairs, nothing is padded, clamped or filtered on the host.  The call is EAGER whatever the
+    ``output_type``: the finished table is converted, ``limit`` takes its head and ``pyarrow.RecordBatchReader`` reads it.  Out
+    of scope: streaming entries (there is no ``window_batches``), sharding over several devices (the call runs on one), join
+    kinds (``how=``) and the overlap thresholds of ``overlap``."""
+    zero_based, t1, t2, probe, build, keys, is_minus, kw = _window_setup(df1, df2, window, upstream, downstream, direction_col, min_distance,
+                                                                         suffixes, on_cols, cols1, cols2, output_type)
+    p_idx, b_idx, dist = default_engine().overlap_window(probe, build, distance=bool(distance), **kw)
+    table = _assemble_overlap(t1, t2, p_idx, b_idx, OverlapOutputMode.Join, False, suffixes, keys)
+    if distance:
+        if not signed_distance:
+            dist = np.abs(dist)
+        elif is_minus is not None and is_minus.any():
+            dist = np.where(is_minus[p_idx], -dist, dist)
+        table = table.append_column("distance", pa.array(dist, type=pa.int64()))
+    return _finish_eager(table, output_type, zero_based, limit)
+
+
+def count_window(
+    df1,
+    df2,
+    window: int = 1000,
+    *,
+    upstream: Union[int, None] = None,
+    downstream: Union[int, None] = None,
+    direction_col: Union[str, None] = None,
+    min_distance: int = 0,
+    suffixes: tuple = ("", "_"),
+    on_cols: Union[list, None] = None,
+    cols1: Union[list, None] = ["chrom", "start", "end"],
+    cols2: Union[list, None] = ["chrom", "start", "end"],
+    output_type: str = "polars.LazyFrame",
+    limit: Union[int, None] = None,
+):
+    """Count the df2 intervals within a distance of every df1 interval: df1's columns + ``count`` (Int64), df1 row order kept, as
+    ``count_overlaps``.  The semantics and the arguments are those of ``window`` (which see); the count of a df1 row equals the
+    number of its rows in ``window``.  The pairs are counted on the device, never enumerated.  Eager, one device, no streaming
+    entry."""
+    zero_based, t1, _t2, probe, build, _keys, _m, kw = _window_setup(df1, df2, window, upstream, downstream, direction_col, min_distance,
+                                                                     suffixes, on_cols, cols1, cols2, output_type)
+    counts = default_engine().count_window(probe, build, **kw)
+    return _finish_eager(t1.append_column("count", pa.array(counts, type=pa.int64())), output_type, zero_based, limit)
 
 
 # ---- sort-scan family (SURVEY.md section 8f row 2) ----------------------------------------------------
