@@ -467,6 +467,12 @@ int check_side(const ivj_side* s, const char* what) {
     if (s->n > 0x7fff0000ll) return fail(IVJ_EINVAL, std::string(what) + ".n exceeds the int32 row-index range");
     return IVJ_OK;
 }
+// the argument prelude of the two-sided host entries: the options, then side a, then side b
+int check_args(const ivj_opts* o, const ivj_side* a, const char* a_name, const ivj_side* b, const char* b_name) {
+    IVJ_TRY(check_opts(o));
+    IVJ_TRY(check_side(a, a_name));
+    return check_side(b, b_name);
+}
 
 IndexView view_of(const ivj_index* ix) {
     IndexView v;

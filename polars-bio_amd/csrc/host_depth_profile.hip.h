@@ -41,32 +41,34 @@ int depth_profile_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* windows, cons
 // takes more than DPROF_CHUNK_BYTES of device memory
 constexpr size_t DPROF_CHUNK_BYTES = (size_t)256 << 20;
 
-int depth_profile_host(ivj_ctx* ctx, const ivj_side* windows, const uint8_t* reverse, int32_t n_bins, const ivj_side* build,
-                       const ivj_opts* opts, int64_t* bases) {
-    DevSide dw, db;
-    IVJ_TRY(upload_side(ctx, build, db));
-    IVJ_TRY(upload_side(ctx, windows, dw));
-    const int64_t n = windows->n;
-    DevBuf rev;
+// what both profile host entries send first: the windows (J.dp) and the build side, the reverse flags (NULL stays NULL), then the index
+int profile_upload(ivj_ctx* ctx, const ivj_side* windows, const uint8_t* reverse, const ivj_side* build, const ivj_opts* opts, JoinHost& J,
+                   DevBuf& rev) {
+    IVJ_TRY(upload_sides(ctx, windows, build, J));
     if (reverse) {
-        hipError_t e = hipMalloc(&rev.p, (size_t)n);
-        if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(reverse): ") + hipGetErrorString(e));
+        IVJ_TRY(devbuf_alloc(rev, (size_t)windows->n, "reverse"));
         HostXfer copy(ctx->stream, &ctx->xfer);
-        copy.h2d(rev.p, reverse, (size_t)n);
+        copy.h2d(rev.p, reverse, (size_t)windows->n);
         HIP_TRY(copy.finish());
     }
-    IndexHolder h;
-    IVJ_TRY(index_build(ctx, &db.s, opts, 0, &h.ix));
+    return index_build(ctx, &J.db.s, opts, 0, &J.h.ix);
+}
+
+int depth_profile_host(ivj_ctx* ctx, const ivj_side* windows, const uint8_t* reverse, int32_t n_bins, const ivj_side* build,
+                       const ivj_opts* opts, int64_t* bases) {
+    JoinHost J;
+    DevBuf rev;
+    IVJ_TRY(profile_upload(ctx, windows, reverse, build, opts, J, rev));
+    const int64_t n = windows->n;
     const size_t row_bytes = (size_t)n_bins * 8;
     const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n, (int64_t)(DPROF_CHUNK_BYTES / row_bytes)));
     DevBuf out;
-    hipError_t e = hipMalloc(&out.p, (size_t)chunk * row_bytes);
-    if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(profile): ") + hipGetErrorString(e));
+    IVJ_TRY(devbuf_alloc(out, (size_t)chunk * row_bytes, "profile"));
     for (int64_t r0 = 0; r0 < n; r0 += chunk) {
         const int64_t m = std::min(chunk, n - r0);
-        ivj_side part = dw.s;
+        ivj_side part = J.dp.s;
         part.contig += r0; part.start += r0; part.end += r0; part.n = m;
-        IVJ_TRY(depth_profile_dev(ctx, h.ix, &part, reverse ? (const uint8_t*)rev.p + r0 : nullptr, n_bins, opts, (int64_t*)out.p));
+        IVJ_TRY(depth_profile_dev(ctx, J.h.ix, &part, reverse ? (const uint8_t*)rev.p + r0 : nullptr, n_bins, opts, (int64_t*)out.p));
         HostXfer copy(ctx->stream, &ctx->xfer);
         copy.d2h(bases + (size_t)r0 * n_bins, out.p, (size_t)m * row_bytes);
         HIP_TRY(copy.finish());                               // the next chunk's kernel writes the same device buffer

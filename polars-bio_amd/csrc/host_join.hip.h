@@ -475,4 +475,60 @@ struct IndexHolder {
     ~IndexHolder() { if (ix) ivj_index_free(ix); }
 };
 
+// ---- the frame of the host-buffer entry points: sides and index into HBM, a device result, the pairs back to the host ----
+
+// both sides of a host-buffer join in HBM, and the index over the build side
+struct JoinHost {
+    DevSide dp, db;
+    IndexHolder h;
+};
+int upload_sides(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, JoinHost& J) {
+    IVJ_TRY(upload_side(ctx, build, J.db));                // the build side first
+    return upload_side(ctx, probe, J.dp);
+}
+int upload_join(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, int index_mode, JoinHost& J) {
+    IVJ_TRY(upload_sides(ctx, probe, build, J));
+    return index_build(ctx, &J.db.s, opts, index_mode, &J.h.ix);
+}
+
+// one frame in HBM and its index
+struct FrameHost {
+    DevSide d;
+    IndexHolder h;
+};
+int upload_frame(ivj_ctx* ctx, const ivj_side* frame, const ivj_opts* opts, int index_mode, FrameHost& F) {
+    IVJ_TRY(upload_side(ctx, frame, F.d));
+    return index_build(ctx, &F.d.s, opts, index_mode, &F.h.ix);
+}
+
+// a device result of a known size; noun words the message
+int devbuf_alloc(DevBuf& b, size_t bytes, const char* noun) {
+    const hipError_t e = hipMalloc(&b.p, bytes);
+    if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(") + noun + "): " + hipGetErrorString(e));
+    return IVJ_OK;
+}
+
+// The device columns of the `total` (> 0) pairs of a host entry, one allocation per column (the emitters store 16-byte vectors from
+// each column's start).  pair_bytes 8: (probe, build); 16: + the int64 distance.  A result the host cannot hold is refused first;
+// fits_tail ends that message (what to call instead differs per entry).
+struct DevPairs {
+    DevBuf p, b, d;
+};
+int alloc_pairs(int64_t total, size_t pair_bytes, const char* fits_tail, DevPairs& P) {
+    if (!host_result_fits((size_t)total * pair_bytes))
+        return fail(IVJ_ENOMEM, "the result (" + std::to_string(total) + " pairs, " + std::to_string((size_t)total * pair_bytes >> 20) +
+                                    " MiB) does not fit the available host memory" + fits_tail);
+    IVJ_TRY(devbuf_alloc(P.p, (size_t)total * 4, "pairs"));
+    IVJ_TRY(devbuf_alloc(P.b, (size_t)total * 4, "pairs"));
+    if (pair_bytes == 16) IVJ_TRY(devbuf_alloc(P.d, (size_t)total * 8, "pairs"));
+    return IVJ_OK;
+}
+// ... and their way into library-allocated host columns; dist NULL: no distance column.  A failure leaves out (and *dist) empty.
+int pairs_to_host(ivj_ctx* ctx, int64_t total, const DevPairs& P, ivj_pairs* out, int64_t** dist = nullptr) {
+    IVJ_TRY(copy_out_columns(ctx, total, {{(void**)&out->probe_idx, P.p.p, 4}, {(void**)&out->build_idx, P.b.p, 4}, {(void**)dist, P.d.p, 8, dist != nullptr}},
+                             "pairs", [&] { ivj_pairs_free(out); if (dist) { std::free(*dist); *dist = nullptr; } }));
+    out->n_pairs = total;
+    return IVJ_OK;
+}
+
 }  // namespace

@@ -313,5 +313,33 @@ struct HostXfer {
     }
 };
 
+// The copy-out of a host entry whose result goes into the caller's buffers: every (dst, src, bytes) to the host, then finish.
+// (0 bytes: an output the caller did not ask for -- HostXfer copies nothing then.)
+struct CopyOut { void* dst; const void* src; size_t bytes; };
+int d2h_finish(ivj_ctx* ctx, std::initializer_list<CopyOut> cols) {
+    HostXfer copy(ctx->stream, &ctx->xfer);
+    for (const CopyOut& c : cols) copy.d2h(c.dst, c.src, c.bytes);
+    HIP_TRY(copy.finish());
+    return IVJ_OK;
+}
+
+// The copy-out of a host entry whose result columns the library allocates: host_result_alloc for every present column of `total`
+// rows, then the copies.  drop() frees what the result struct's own *_free frees; it runs before either failure is reported, so a
+// failed call leaves every column NULL.  The caller sets the row count last.
+struct ResultCol { void** host; const void* dev; size_t elem_bytes; bool present = true; };
+template <class Drop>
+int copy_out_columns(ivj_ctx* ctx, int64_t total, std::initializer_list<ResultCol> cols, const char* noun, Drop drop) {
+    bool ok = true;
+    for (const ResultCol& c : cols)
+        if (c.present && !(*c.host = host_result_alloc((size_t)total * c.elem_bytes))) ok = false;
+    if (!ok) { drop(); return fail(IVJ_ENOMEM, std::string("host malloc(") + noun + ")"); }
+    HostXfer copy(ctx->stream, &ctx->xfer);
+    for (const ResultCol& c : cols)
+        if (c.present) copy.d2h(*c.host, c.dev, (size_t)total * c.elem_bytes);
+    const hipError_t e = copy.finish();
+    if (e != hipSuccess) { drop(); return fail(IVJ_EHIP, std::string("D2H(") + noun + "): " + hipGetErrorString(e)); }
+    return IVJ_OK;
+}
+
 }  // namespace
 

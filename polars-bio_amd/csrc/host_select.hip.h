@@ -108,9 +108,7 @@ int select_upload(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, co
         U.dthr = &U.H.dthr;
         return IVJ_OK;
     }
-    IVJ_TRY(upload_side(ctx, build, U.H.db));
-    IVJ_TRY(upload_side(ctx, probe, U.H.dp));
-    return index_build(ctx, &U.H.db.s, opts, 1, &U.H.h.ix);
+    return upload_join(ctx, probe, build, opts, 1, U.H);
 }
 
 }  // namespace

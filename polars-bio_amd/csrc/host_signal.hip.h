@@ -33,9 +33,7 @@ int overlap_wagg_col(ivj_ctx* ctx, ivj_index* ix, const OaggPlan& P, const ivj_a
 // sides (and minima) into HBM + the index; the thresholded walk needs no end order
 int overlap_wagg_upload(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, const ivj_thresholds* thr, SelectHost& U) {
     if (thr) return select_upload(ctx, probe, build, opts, thr, U);
-    IVJ_TRY(upload_side(ctx, build, U.H.db));
-    IVJ_TRY(upload_side(ctx, probe, U.H.dp));
-    return index_build(ctx, &U.H.db.s, opts, 0, &U.H.h.ix);
+    return upload_join(ctx, probe, build, opts, 0, U.H);
 }
 
 // ---- signal_profile: the bins of the windows as probes ----------------------------------------------------------------------------
@@ -95,26 +93,16 @@ int signal_profile_check(const ivj_opts* opts, const ivj_side* windows, int32_t 
 // never take more than 5 x DPROF_CHUNK_BYTES of device memory (the value column is sent again per chunk).
 int signal_profile_host(ivj_ctx* ctx, const ivj_side* windows, const uint8_t* reverse, int32_t n_bins, const ivj_side* build,
                         const ivj_opts* opts, int32_t n_cols, const ivj_agg_in* cols, const ivj_agg_out* agg_out) {
-    DevSide dw, db;
-    IVJ_TRY(upload_side(ctx, build, db));
-    IVJ_TRY(upload_side(ctx, windows, dw));
-    const int64_t n = windows->n, nb = build->n;
+    JoinHost J;
     DevBuf rev;
-    if (reverse) {
-        hipError_t e = hipMalloc(&rev.p, (size_t)n);
-        if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(reverse): ") + hipGetErrorString(e));
-        HostXfer copy(ctx->stream, &ctx->xfer);
-        copy.h2d(rev.p, reverse, (size_t)n);
-        HIP_TRY(copy.finish());
-    }
-    IndexHolder h;
-    IVJ_TRY(index_build(ctx, &db.s, opts, 0, &h.ix));
+    IVJ_TRY(profile_upload(ctx, windows, reverse, build, opts, J, rev));
+    const int64_t n = windows->n, nb = build->n;
     const size_t row_bytes = (size_t)n_bins * 8;
     const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n, (int64_t)(DPROF_CHUNK_BYTES / row_bytes)));
     std::vector<ivj_agg_out> part_out((size_t)n_cols);
     for (int64_t r0 = 0; r0 < n; r0 += chunk) {
         const int64_t m = std::min(chunk, n - r0);
-        ivj_side part = dw.s;
+        ivj_side part = J.dp.s;
         part.contig += r0; part.start += r0; part.end += r0; part.n = m;
         const uint8_t* prev = reverse ? (const uint8_t*)rev.p + r0 : nullptr;
         const size_t at = (size_t)r0 * (size_t)n_bins;
@@ -124,9 +112,9 @@ int signal_profile_host(ivj_ctx* ctx, const ivj_side* windows, const uint8_t* re
                                       o.max ? (char*)o.max + at * 8 : nullptr, o.mean ? o.mean + at : nullptr, o.count ? o.count + at : nullptr};
         }
         OaggPlan P;
-        IVJ_TRY(signal_profile_plan(ctx, h.ix, &part, n_bins, opts, P));
+        IVJ_TRY(signal_profile_plan(ctx, J.h.ix, &part, n_bins, opts, P));
         IVJ_TRY(agg_cols_host(ctx, P.n, nb, n_cols, cols, part_out.data(), [&](const ivj_agg_in& in, const ivj_agg_out& dev) {
-            return signal_profile_col(ctx, h.ix, P, prev, m, n_bins, in, nb, dev);
+            return signal_profile_col(ctx, J.h.ix, P, prev, m, n_bins, in, nb, dev);
         }));
     }
     return IVJ_OK;

@@ -110,15 +110,12 @@ int upload_min(ivj_ctx* ctx, const uint32_t* h, int64_t n, DevMin& d) {
 }
 
 // both host entries: sides, minima and index into HBM; dthr receives the device form of the thresholds
-struct ThreshHost {
-    DevSide dp, db;
+struct ThreshHost : JoinHost {
     DevMin pm, bm;
-    IndexHolder h;
     ivj_thresholds dthr{0, nullptr, nullptr};
 };
 int thresh_upload(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, const ivj_thresholds* thr, ThreshHost& H) {
-    IVJ_TRY(upload_side(ctx, build, H.db));
-    IVJ_TRY(upload_side(ctx, probe, H.dp));
+    IVJ_TRY(upload_sides(ctx, probe, build, H));
     IVJ_TRY(upload_min(ctx, thr->probe_min, probe->n, H.pm));
     IVJ_TRY(upload_min(ctx, thr->build_min, build->n, H.bm));
     H.dthr.min_overlap = thr->min_overlap; H.dthr.probe_min = H.pm.p; H.dthr.build_min = H.bm.p;

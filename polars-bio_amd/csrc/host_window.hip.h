@@ -91,15 +91,12 @@ int overlap_window_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe, const
 }
 
 // both host entries: sides, per-row extents and index into HBM; dwin receives the device form of the window
-struct WindowHost {
-    DevSide dp, db;
+struct WindowHost : JoinHost {
     DevMin pl, pr;
-    IndexHolder h;
     ivj_window dwin{0, 0, nullptr, nullptr, 0};
 };
 int window_upload(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, const ivj_window* win, WindowHost& H) {
-    IVJ_TRY(upload_side(ctx, build, H.db));
-    IVJ_TRY(upload_side(ctx, probe, H.dp));
+    IVJ_TRY(upload_sides(ctx, probe, build, H));
     IVJ_TRY(upload_min(ctx, win->probe_left, probe->n, H.pl));
     IVJ_TRY(upload_min(ctx, win->probe_right, probe->n, H.pr));
     H.dwin = *win;

@@ -17,6 +17,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 #include <thread>
@@ -527,35 +528,17 @@ int ivj_nearest_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, cons
 int ivj_overlap(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, ivj_pairs* out) try {
     if (!ctx || !out) return fail(IVJ_EINVAL, "ctx or out is NULL");
     out->n_pairs = 0; out->probe_idx = nullptr; out->build_idx = nullptr;
-    IVJ_TRY(check_opts(opts));
-    IVJ_TRY(check_side(probe, "probe"));
-    IVJ_TRY(check_side(build, "build"));
+    IVJ_TRY(check_args(opts, probe, "probe", build, "build"));
     DeviceGuard g(ctx->device);
-    DevSide dp, db;
-    IVJ_TRY(upload_side(ctx, build, db));
-    IVJ_TRY(upload_side(ctx, probe, dp));
-    IndexHolder h;
-    IVJ_TRY(index_build(ctx, &db.s, opts, 0, &h.ix));
+    JoinHost J;
+    IVJ_TRY(upload_join(ctx, probe, build, opts, 0, J));
     int64_t total = 0;
-    IVJ_TRY(overlap_count(ctx, h.ix, &dp.s, opts, &total));
+    IVJ_TRY(overlap_count(ctx, J.h.ix, &J.dp.s, opts, &total));
     if (total == 0) return IVJ_OK;
-    if (!host_result_fits((size_t)total * 8))
-        return fail(IVJ_ENOMEM, "the result (" + std::to_string(total) + " pairs, " + std::to_string((size_t)total * 8 >> 20) + " MiB) does not fit the available host memory; use the streaming entry points (ivj_stream_*) or the *_dev ones");
-    DevBuf op, ob;
-    hipError_t e = hipMalloc(&op.p, (size_t)total * 4);
-    if (e == hipSuccess) e = hipMalloc(&ob.p, (size_t)total * 4);
-    if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(pairs): ") + hipGetErrorString(e));
-    IVJ_TRY(overlap_fill(ctx, h.ix, &dp.s, opts, (int32_t*)op.p, (int32_t*)ob.p, total));
-    out->probe_idx = (int32_t*)host_result_alloc((size_t)total * 4);
-    out->build_idx = (int32_t*)host_result_alloc((size_t)total * 4);
-    if (!out->probe_idx || !out->build_idx) { ivj_pairs_free(out); return fail(IVJ_ENOMEM, "host malloc(pairs)"); }
-    HostXfer copy(ctx->stream, &ctx->xfer);
-    copy.d2h(out->probe_idx, op.p, (size_t)total * 4);
-    copy.d2h(out->build_idx, ob.p, (size_t)total * 4);
-    const hipError_t ce = copy.finish();
-    if (ce != hipSuccess) { ivj_pairs_free(out); return fail(IVJ_EHIP, std::string("D2H(pairs): ") + hipGetErrorString(ce)); }
-    out->n_pairs = total;
-    return IVJ_OK;
+    DevPairs P;
+    IVJ_TRY(alloc_pairs(total, 8, "; use the streaming entry points (ivj_stream_*) or the *_dev ones", P));
+    IVJ_TRY(overlap_fill(ctx, J.h.ix, &J.dp.s, opts, (int32_t*)P.p.p, (int32_t*)P.b.p, total));
+    return pairs_to_host(ctx, total, P, out);
 } IVJ_ABI_CATCH
 
 // ---------------------------------------------------------------- merge / cluster / coverage
@@ -629,26 +612,14 @@ int ivj_merge(ivj_ctx* ctx, const ivj_side* side, const ivj_opts* opts, int64_t 
     if (min_dist < 0) return fail(IVJ_EINVAL, "min_dist < 0");
     if (side->n == 0) return IVJ_OK;
     DeviceGuard g(ctx->device);
-    DevSide ds;
-    IVJ_TRY(upload_side(ctx, side, ds));
-    IndexHolder h;
-    IVJ_TRY(index_build(ctx, &ds.s, opts, 2, &h.ix));      // sweep only: no lookup tables
+    FrameHost F;
+    IVJ_TRY(upload_frame(ctx, side, opts, 2, F));          // sweep only: no lookup tables
     Clusters cl;
-    IVJ_TRY(cluster_core(ctx, h.ix, opts->filter_op == IVJ_FILTER_STRICT, (long long)min_dist, align_up((size_t)(side->n + 1) * 8), cl));
+    IVJ_TRY(cluster_core(ctx, F.h.ix, opts->filter_op == IVJ_FILTER_STRICT, (long long)min_dist, align_up((size_t)(side->n + 1) * 8), cl));
     long long* cnt = arena_take<long long>(ctx, side->n + 1);
     LAUNCH(ctx, "cluster_counts", k_cluster_counts, grid1d(cl.n, 256), 256, (const int32_t*)cl.m_first, cl.n, cnt);
-    out->contig = (int32_t*)host_result_alloc((size_t)cl.n * 4);
-    out->start = (int32_t*)host_result_alloc((size_t)cl.n * 4);
-    out->end = (int32_t*)host_result_alloc((size_t)cl.n * 4);
-    out->n_intervals = (int64_t*)host_result_alloc((size_t)cl.n * 8);
-    if (!out->contig || !out->start || !out->end || !out->n_intervals) { ivj_merged_free(out); return fail(IVJ_ENOMEM, "host malloc(merged)"); }
-    HostXfer copy(ctx->stream, &ctx->xfer);
-    copy.d2h(out->contig, cl.m_contig, (size_t)cl.n * 4);
-    copy.d2h(out->start, cl.m_start, (size_t)cl.n * 4);
-    copy.d2h(out->end, cl.m_end, (size_t)cl.n * 4);
-    copy.d2h(out->n_intervals, cnt, (size_t)cl.n * 8);
-    const hipError_t e = copy.finish();
-    if (e != hipSuccess) { ivj_merged_free(out); return fail(IVJ_EHIP, std::string("D2H(merged): ") + hipGetErrorString(e)); }
+    IVJ_TRY(copy_out_columns(ctx, cl.n, {{(void**)&out->contig, cl.m_contig, 4}, {(void**)&out->start, cl.m_start, 4}, {(void**)&out->end, cl.m_end, 4},
+                                         {(void**)&out->n_intervals, cnt, 8}}, "merged", [&] { ivj_merged_free(out); }));
     out->n = cl.n;
     return IVJ_OK;
 } IVJ_ABI_CATCH
@@ -702,14 +673,12 @@ int ivj_merge_agg(ivj_ctx* ctx, const ivj_side* side, const ivj_opts* opts, int6
     if (side->n == 0) return IVJ_OK;
     const int64_t n = side->n;
     DeviceGuard g(ctx->device);
-    DevSide ds;
-    IVJ_TRY(upload_side(ctx, side, ds));
-    IndexHolder h;
-    IVJ_TRY(index_build(ctx, &ds.s, opts, 2, &h.ix));      // sweep only: no lookup tables
+    FrameHost F;
+    IVJ_TRY(upload_frame(ctx, side, opts, 2, F));          // sweep only: no lookup tables
     // arena: the count column, the tile parts, one value column with its validity bytes, the five result columns of one value column
     const size_t col8 = align_up((size_t)(n + 1) * 8);
     Clusters cl;
-    IVJ_TRY(cluster_core(ctx, h.ix, opts->filter_op == IVJ_FILTER_STRICT, (long long)min_dist,
+    IVJ_TRY(cluster_core(ctx, F.h.ix, opts->filter_op == IVJ_FILTER_STRICT, (long long)min_dist,
                          col8 + merge_agg_bytes(n) + col8 + align_up((size_t)n + 1) + 5 * col8, cl));
     long long* cnt = arena_take<long long>(ctx, n + 1);
     void* part = arena_take<AggState<double>>(ctx, 2 * magg_num_tiles(n) + 1);
@@ -748,7 +717,7 @@ int ivj_merge_agg(ivj_ctx* ctx, const ivj_side* side, const ivj_opts* opts, int6
             copy.h2d(d_val, cols[k].values, (size_t)n * 8);
             if (cols[k].valid) copy.h2d(d_valid, cols[k].valid, (size_t)n);
             const ivj_agg_in in{d_val, cols[k].valid ? d_valid : nullptr, cols[k].dtype, cols[k].ops};
-            rc = merge_agg_col(ctx, h.ix, cl, in, n, dev, part);
+            rc = merge_agg_col(ctx, F.h.ix, cl, in, n, dev, part);
             const ivj_agg_out& o = agg_out[k];
             if (o.sum) copy.d2h(o.sum, dev.sum, m8);
             if (o.min) copy.d2h(o.min, dev.min, m8);
@@ -774,72 +743,47 @@ int ivj_cluster(ivj_ctx* ctx, const ivj_side* side, const ivj_opts* opts, int64_
     if (side->n == 0) return IVJ_OK;
     if (!cluster || !cluster_start || !cluster_end) return fail(IVJ_EINVAL, "cluster output buffers are NULL");
     DeviceGuard g(ctx->device);
-    DevSide ds;
-    IVJ_TRY(upload_side(ctx, side, ds));
-    IndexHolder h;
-    IVJ_TRY(index_build(ctx, &ds.s, opts, 2, &h.ix));      // sweep only: no lookup tables
+    FrameHost F;
+    IVJ_TRY(upload_frame(ctx, side, opts, 2, F));          // sweep only: no lookup tables
     DevBuf out;
     const size_t n = (size_t)side->n;
-    hipError_t e = hipMalloc(&out.p, align_up(n * 8) + 2 * align_up(n * 4));
-    if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(cluster): ") + hipGetErrorString(e));
+    IVJ_TRY(devbuf_alloc(out, align_up(n * 8) + 2 * align_up(n * 4), "cluster"));
     int64_t* d_c = (int64_t*)out.p;
     int32_t* d_s = (int32_t*)((char*)out.p + align_up(n * 8));
     int32_t* d_e = (int32_t*)((char*)d_s + align_up(n * 4));
     int64_t ncl = 0;
-    IVJ_TRY(ivj_cluster_dev(ctx, h.ix, opts, min_dist, d_c, d_s, d_e, &ncl));
-    HostXfer copy(ctx->stream, &ctx->xfer);
-    copy.d2h(cluster, d_c, n * 8);
-    copy.d2h(cluster_start, d_s, n * 4);
-    copy.d2h(cluster_end, d_e, n * 4);
-    HIP_TRY(copy.finish());
+    IVJ_TRY(ivj_cluster_dev(ctx, F.h.ix, opts, min_dist, d_c, d_s, d_e, &ncl));
+    IVJ_TRY(d2h_finish(ctx, {{cluster, d_c, n * 8}, {cluster_start, d_s, n * 4}, {cluster_end, d_e, n * 4}}));
     if (n_clusters) *n_clusters = ncl;
     return IVJ_OK;
 } IVJ_ABI_CATCH
 
 int ivj_coverage(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, int64_t* coverage) try {
     if (!ctx) return fail(IVJ_EINVAL, "ctx is NULL");
-    IVJ_TRY(check_opts(opts));
-    IVJ_TRY(check_side(probe, "probe"));
-    IVJ_TRY(check_side(build, "build"));
+    IVJ_TRY(check_args(opts, probe, "probe", build, "build"));
     if (probe->n == 0) return IVJ_OK;
     if (!coverage) return fail(IVJ_EINVAL, "coverage is NULL");
     DeviceGuard g(ctx->device);
-    DevSide dp, db;
-    IVJ_TRY(upload_side(ctx, build, db));
-    IVJ_TRY(upload_side(ctx, probe, dp));
-    IndexHolder h;
-    IVJ_TRY(index_build(ctx, &db.s, opts, 0, &h.ix));
+    JoinHost J;
+    IVJ_TRY(upload_join(ctx, probe, build, opts, 0, J));
     DevBuf out;
-    hipError_t e = hipMalloc(&out.p, (size_t)probe->n * 8);
-    if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(coverage): ") + hipGetErrorString(e));
-    IVJ_TRY(coverage_core(ctx, h.ix, &dp.s, opts, (int64_t*)out.p));
-    HostXfer copy(ctx->stream, &ctx->xfer);
-    copy.d2h(coverage, out.p, (size_t)probe->n * 8);
-    HIP_TRY(copy.finish());
-    return IVJ_OK;
+    IVJ_TRY(devbuf_alloc(out, (size_t)probe->n * 8, "coverage"));
+    IVJ_TRY(coverage_core(ctx, J.h.ix, &J.dp.s, opts, (int64_t*)out.p));
+    return d2h_finish(ctx, {{coverage, out.p, (size_t)probe->n * 8}});
 } IVJ_ABI_CATCH
 
 int ivj_overlap_bases(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, int64_t* bases) try {
     if (!ctx) return fail(IVJ_EINVAL, "ctx is NULL");
-    IVJ_TRY(check_opts(opts));
-    IVJ_TRY(check_side(probe, "probe"));
-    IVJ_TRY(check_side(build, "build"));
+    IVJ_TRY(check_args(opts, probe, "probe", build, "build"));
     if (probe->n == 0) return IVJ_OK;
     if (!bases) return fail(IVJ_EINVAL, "bases is NULL");
     DeviceGuard g(ctx->device);
-    DevSide dp, db;
-    IVJ_TRY(upload_side(ctx, build, db));
-    IVJ_TRY(upload_side(ctx, probe, dp));
-    IndexHolder h;
-    IVJ_TRY(index_build(ctx, &db.s, opts, 0, &h.ix));
+    JoinHost J;
+    IVJ_TRY(upload_join(ctx, probe, build, opts, 0, J));
     DevBuf out;
-    hipError_t e = hipMalloc(&out.p, (size_t)probe->n * 8);
-    if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(bases): ") + hipGetErrorString(e));
-    IVJ_TRY(depth_sum_dev(ctx, h.ix, &dp.s, opts, (int64_t*)out.p));
-    HostXfer copy(ctx->stream, &ctx->xfer);
-    copy.d2h(bases, out.p, (size_t)probe->n * 8);
-    HIP_TRY(copy.finish());
-    return IVJ_OK;
+    IVJ_TRY(devbuf_alloc(out, (size_t)probe->n * 8, "bases"));
+    IVJ_TRY(depth_sum_dev(ctx, J.h.ix, &J.dp.s, opts, (int64_t*)out.p));
+    return d2h_finish(ctx, {{bases, out.p, (size_t)probe->n * 8}});
 } IVJ_ABI_CATCH
 
 // ---------------------------------------------------------------- depth profile (per-bin base sums of every window row)
@@ -858,9 +802,7 @@ int ivj_depth_profile_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* windows_d
 int ivj_depth_profile(ivj_ctx* ctx, const ivj_side* windows, const uint8_t* reverse, int32_t n_bins, const ivj_side* build,
                       const ivj_opts* opts, int64_t* bases) try {
     if (!ctx) return fail(IVJ_EINVAL, "ctx is NULL");
-    IVJ_TRY(check_opts(opts));
-    IVJ_TRY(check_side(windows, "windows"));
-    IVJ_TRY(check_side(build, "build"));
+    IVJ_TRY(check_args(opts, windows, "windows", build, "build"));
     IVJ_TRY(depth_profile_check(n_bins));
     if (windows->n == 0) return IVJ_OK;
     if (!bases) return fail(IVJ_EINVAL, "bases is NULL");
@@ -892,27 +834,15 @@ int ivj_depth(ivj_ctx* ctx, const ivj_side* frame, const ivj_opts* opts, ivj_blo
     IVJ_TRY(check_side(frame, "frame"));
     if (frame->n == 0) return IVJ_OK;
     DeviceGuard g(ctx->device);
-    DevSide ds;
-    IVJ_TRY(upload_side(ctx, frame, ds));
-    IndexHolder h;
-    IVJ_TRY(index_build(ctx, &ds.s, opts, 3, &h.ix));      // sweep only (no lookup tables) + the end order
+    FrameHost F;
+    IVJ_TRY(upload_frame(ctx, frame, opts, 3, F));         // sweep only (no lookup tables) + the end order
     DevBuf own;
     int32_t *d_contig = nullptr, *d_start = nullptr, *d_end = nullptr, *d_depth = nullptr;
     int64_t total = 0;
-    IVJ_TRY(depth_core(ctx, h.ix, opts, -1, &d_contig, &d_start, &d_end, &d_depth, &own, &total));
+    IVJ_TRY(depth_core(ctx, F.h.ix, opts, -1, &d_contig, &d_start, &d_end, &d_depth, &own, &total));
     if (total == 0) return IVJ_OK;
-    out->contig = (int32_t*)host_result_alloc((size_t)total * 4);
-    out->start = (int32_t*)host_result_alloc((size_t)total * 4);
-    out->end = (int32_t*)host_result_alloc((size_t)total * 4);
-    out->depth = (int32_t*)host_result_alloc((size_t)total * 4);
-    if (!out->contig || !out->start || !out->end || !out->depth) { ivj_blocks_free(out); return fail(IVJ_ENOMEM, "host malloc(blocks)"); }
-    HostXfer copy(ctx->stream, &ctx->xfer);
-    copy.d2h(out->contig, d_contig, (size_t)total * 4);
-    copy.d2h(out->start, d_start, (size_t)total * 4);
-    copy.d2h(out->end, d_end, (size_t)total * 4);
-    copy.d2h(out->depth, d_depth, (size_t)total * 4);
-    const hipError_t e = copy.finish();
-    if (e != hipSuccess) { ivj_blocks_free(out); return fail(IVJ_EHIP, std::string("D2H(blocks): ") + hipGetErrorString(e)); }
+    IVJ_TRY(copy_out_columns(ctx, total, {{(void**)&out->contig, d_contig, 4}, {(void**)&out->start, d_start, 4}, {(void**)&out->end, d_end, 4},
+                                          {(void**)&out->depth, d_depth, 4}}, "blocks", [&] { ivj_blocks_free(out); }));
     out->n = total;
     return IVJ_OK;
 } IVJ_ABI_CATCH
@@ -932,29 +862,19 @@ int ivj_depth_summary_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev
 int ivj_depth_summary(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, const int32_t* thresholds,
                       int32_t n_thresholds, int32_t* max_depth, int64_t* bases_ge) try {
     if (!ctx) return fail(IVJ_EINVAL, "ctx is NULL");
-    IVJ_TRY(check_opts(opts));
-    IVJ_TRY(check_side(probe, "probe"));
-    IVJ_TRY(check_side(build, "build"));
+    IVJ_TRY(check_args(opts, probe, "probe", build, "build"));
     IVJ_TRY(depth_query_check(thresholds, n_thresholds, max_depth, bases_ge));
     if (probe->n == 0) return IVJ_OK;
     DeviceGuard g(ctx->device);
-    DevSide dp, db;
-    IVJ_TRY(upload_side(ctx, build, db));
-    IVJ_TRY(upload_side(ctx, probe, dp));
-    IndexHolder h;
-    IVJ_TRY(index_build(ctx, &db.s, opts, 3, &h.ix));      // sweep only (no lookup tables) + the end order: what depth_core reads
+    JoinHost J;
+    IVJ_TRY(upload_join(ctx, probe, build, opts, 3, J));   // sweep only (no lookup tables) + the end order: what depth_core reads
     const size_t n = (size_t)probe->n, md_bytes = align_up(n * 4), col_bytes = n * 8;
     DevBuf out;
-    hipError_t e = hipMalloc(&out.p, md_bytes + (size_t)n_thresholds * col_bytes + 256);
-    if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(depth summary): ") + hipGetErrorString(e));
+    IVJ_TRY(devbuf_alloc(out, md_bytes + (size_t)n_thresholds * col_bytes + 256, "depth summary"));
     int32_t* d_md = max_depth ? (int32_t*)out.p : nullptr;
     int64_t* d_bg = n_thresholds > 0 ? (int64_t*)((char*)out.p + md_bytes) : nullptr;
-    IVJ_TRY(depth_query_dev(ctx, h.ix, &dp.s, opts, thresholds, n_thresholds, d_md, d_bg));
-    HostXfer copy(ctx->stream, &ctx->xfer);
-    if (d_md) copy.d2h(max_depth, d_md, n * 4);
-    if (d_bg) copy.d2h(bases_ge, d_bg, (size_t)n_thresholds * col_bytes);
-    HIP_TRY(copy.finish());
-    return IVJ_OK;
+    IVJ_TRY(depth_query_dev(ctx, J.h.ix, &J.dp.s, opts, thresholds, n_thresholds, d_md, d_bg));
+    return d2h_finish(ctx, {{max_depth, d_md, d_md ? n * 4 : 0}, {bases_ge, d_bg, d_bg ? (size_t)n_thresholds * col_bytes : 0}});
 } IVJ_ABI_CATCH
 
 // ---------------------------------------------------------------- depth histogram (positions at each depth, per row / per contig)
@@ -970,26 +890,17 @@ int ivj_depth_hist_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, c
 
 int ivj_depth_hist(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, int32_t max_depth, int64_t* hist) try {
     if (!ctx) return fail(IVJ_EINVAL, "ctx is NULL");
-    IVJ_TRY(check_opts(opts));
-    IVJ_TRY(check_side(probe, "probe"));
-    IVJ_TRY(check_side(build, "build"));
+    IVJ_TRY(check_args(opts, probe, "probe", build, "build"));
     IVJ_TRY(depth_hist_check(max_depth, hist));
     if (probe->n == 0) return IVJ_OK;
     DeviceGuard g(ctx->device);
-    DevSide dp, db;
-    IVJ_TRY(upload_side(ctx, build, db));
-    IVJ_TRY(upload_side(ctx, probe, dp));
-    IndexHolder h;
-    IVJ_TRY(index_build(ctx, &db.s, opts, 3, &h.ix));      // sweep only (no lookup tables) + the end order: what depth_core reads
+    JoinHost J;
+    IVJ_TRY(upload_join(ctx, probe, build, opts, 3, J));   // sweep only (no lookup tables) + the end order: what depth_core reads
     const size_t bytes = (size_t)probe->n * (size_t)(max_depth + 1) * 8;
     DevBuf out;
-    const hipError_t e = hipMalloc(&out.p, bytes);
-    if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(depth histogram): ") + hipGetErrorString(e));
-    IVJ_TRY(depth_hist_dev(ctx, h.ix, &dp.s, opts, max_depth, (int64_t*)out.p));
-    HostXfer copy(ctx->stream, &ctx->xfer);
-    copy.d2h(hist, out.p, bytes);
-    HIP_TRY(copy.finish());
-    return IVJ_OK;
+    IVJ_TRY(devbuf_alloc(out, bytes, "depth histogram"));
+    IVJ_TRY(depth_hist_dev(ctx, J.h.ix, &J.dp.s, opts, max_depth, (int64_t*)out.p));
+    return d2h_finish(ctx, {{hist, out.p, bytes}});
 } IVJ_ABI_CATCH
 
 int ivj_depth_hist_contigs_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_opts* opts, int32_t max_depth, int64_t* hist_dev) try {
@@ -1009,18 +920,12 @@ int ivj_depth_hist_contigs(ivj_ctx* ctx, const ivj_side* frame, const ivj_opts* 
     const size_t bytes = (size_t)opts->n_contigs * (size_t)(max_depth + 1) * 8;
     if (frame->n == 0) { std::memset(hist, 0, bytes); return IVJ_OK; }
     DeviceGuard g(ctx->device);
-    DevSide ds;
-    IVJ_TRY(upload_side(ctx, frame, ds));
-    IndexHolder h;
-    IVJ_TRY(index_build(ctx, &ds.s, opts, 3, &h.ix));      // sweep only (no lookup tables) + the end order
+    FrameHost F;
+    IVJ_TRY(upload_frame(ctx, frame, opts, 3, F));         // sweep only (no lookup tables) + the end order
     DevBuf out;
-    const hipError_t e = hipMalloc(&out.p, bytes);
-    if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(depth histogram): ") + hipGetErrorString(e));
-    IVJ_TRY(depth_hist_contigs_dev(ctx, h.ix, opts, max_depth, (int64_t*)out.p));
-    HostXfer copy(ctx->stream, &ctx->xfer);
-    copy.d2h(hist, out.p, bytes);
-    HIP_TRY(copy.finish());
-    return IVJ_OK;
+    IVJ_TRY(devbuf_alloc(out, bytes, "depth histogram"));
+    IVJ_TRY(depth_hist_contigs_dev(ctx, F.h.ix, opts, max_depth, (int64_t*)out.p));
+    return d2h_finish(ctx, {{hist, out.p, bytes}});
 } IVJ_ABI_CATCH
 
 // ---------------------------------------------------------------- depth quantiles (order statistics of the depth, per row)
@@ -1038,21 +943,15 @@ int ivj_depth_quantiles_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_d
 int ivj_depth_quantiles(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, int32_t n_ranks, const int64_t* ranks,
                         int32_t* out) try {
     if (!ctx) return fail(IVJ_EINVAL, "ctx is NULL");
-    IVJ_TRY(check_opts(opts));
-    IVJ_TRY(check_side(probe, "probe"));
-    IVJ_TRY(check_side(build, "build"));
+    IVJ_TRY(check_args(opts, probe, "probe", build, "build"));
     IVJ_TRY(depth_quant_check(n_ranks, ranks, out));
     if (probe->n == 0) return IVJ_OK;
     DeviceGuard g(ctx->device);
-    DevSide dp, db;
-    IVJ_TRY(upload_side(ctx, build, db));
-    IVJ_TRY(upload_side(ctx, probe, dp));
-    IndexHolder h;
-    IVJ_TRY(index_build(ctx, &db.s, opts, 3, &h.ix));      // sweep only (no lookup tables) + the end order: what depth_core reads
+    JoinHost J;
+    IVJ_TRY(upload_join(ctx, probe, build, opts, 3, J));   // sweep only (no lookup tables) + the end order: what depth_core reads
     const size_t cells = (size_t)probe->n * (size_t)n_ranks;
     DevBuf buf;                                            // the ranks, then the answers
-    const hipError_t e = hipMalloc(&buf.p, cells * 12);
-    if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(depth quantiles): ") + hipGetErrorString(e));
+    IVJ_TRY(devbuf_alloc(buf, cells * 12, "depth quantiles"));
     int64_t* d_ranks = (int64_t*)buf.p;
     int32_t* d_out = (int32_t*)(d_ranks + cells);
     {
@@ -1060,11 +959,8 @@ int ivj_depth_quantiles(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* bui
         copy.h2d(d_ranks, ranks, cells * 8);
         HIP_TRY(copy.finish());
     }
-    IVJ_TRY(depth_quant_dev(ctx, h.ix, &dp.s, opts, n_ranks, d_ranks, d_out));
-    HostXfer copy(ctx->stream, &ctx->xfer);
-    copy.d2h(out, d_out, cells * 4);
-    HIP_TRY(copy.finish());
-    return IVJ_OK;
+    IVJ_TRY(depth_quant_dev(ctx, J.h.ix, &J.dp.s, opts, n_ranks, d_ranks, d_out));
+    return d2h_finish(ctx, {{out, d_out, cells * 4}});
 } IVJ_ABI_CATCH
 
 // ---------------------------------------------------------------- set operations on two frames, and their stats
@@ -1094,12 +990,11 @@ void ivj_regions_free(ivj_regions* r) {
 namespace {
 // both sides of a host-path set operation: uploaded and indexed (sweep only + the end order); an empty side stays without an index
 struct SetSides {
-    DevSide da, db;
-    IndexHolder ha, hb;
+    FrameHost a, b;
 };
 int setop_sides(ivj_ctx* ctx, const ivj_side* a, const ivj_side* b, const ivj_opts* opts, SetSides& s) {
-    if (a->n > 0) { IVJ_TRY(upload_side(ctx, a, s.da)); IVJ_TRY(index_build(ctx, &s.da.s, opts, 3, &s.ha.ix)); }
-    if (b->n > 0) { IVJ_TRY(upload_side(ctx, b, s.db)); IVJ_TRY(index_build(ctx, &s.db.s, opts, 3, &s.hb.ix)); }
+    if (a->n > 0) IVJ_TRY(upload_frame(ctx, a, opts, 3, s.a));
+    if (b->n > 0) IVJ_TRY(upload_frame(ctx, b, opts, 3, s.b));
     return IVJ_OK;
 }
 }  // namespace
@@ -1107,40 +1002,28 @@ int setop_sides(ivj_ctx* ctx, const ivj_side* a, const ivj_side* b, const ivj_op
 int ivj_setop(ivj_ctx* ctx, const ivj_side* a, const ivj_side* b, const ivj_opts* opts, int32_t op, ivj_regions* out) try {
     if (!ctx || !out) return fail(IVJ_EINVAL, "ctx or out is NULL");
     std::memset(out, 0, sizeof(*out));
-    IVJ_TRY(check_opts(opts));
-    IVJ_TRY(check_side(a, "a"));
-    IVJ_TRY(check_side(b, "b"));
+    IVJ_TRY(check_args(opts, a, "a", b, "b"));
     DeviceGuard g(ctx->device);
     SetSides s;
     IVJ_TRY(setop_sides(ctx, a, b, opts, s));
     DevBuf own;
     int32_t *d_contig = nullptr, *d_start = nullptr, *d_end = nullptr;
     int64_t total = 0;
-    IVJ_TRY(setop_core(ctx, s.ha.ix, s.hb.ix, opts, op, -1, &d_contig, &d_start, &d_end, &own, &total));
+    IVJ_TRY(setop_core(ctx, s.a.h.ix, s.b.h.ix, opts, op, -1, &d_contig, &d_start, &d_end, &own, &total));
     if (total == 0) return IVJ_OK;
-    out->contig = (int32_t*)host_result_alloc((size_t)total * 4);
-    out->start = (int32_t*)host_result_alloc((size_t)total * 4);
-    out->end = (int32_t*)host_result_alloc((size_t)total * 4);
-    if (!out->contig || !out->start || !out->end) { ivj_regions_free(out); return fail(IVJ_ENOMEM, "host malloc(regions)"); }
-    HostXfer copy(ctx->stream, &ctx->xfer);
-    copy.d2h(out->contig, d_contig, (size_t)total * 4);
-    copy.d2h(out->start, d_start, (size_t)total * 4);
-    copy.d2h(out->end, d_end, (size_t)total * 4);
-    const hipError_t e = copy.finish();
-    if (e != hipSuccess) { ivj_regions_free(out); return fail(IVJ_EHIP, std::string("D2H(regions): ") + hipGetErrorString(e)); }
+    IVJ_TRY(copy_out_columns(ctx, total, {{(void**)&out->contig, d_contig, 4}, {(void**)&out->start, d_start, 4}, {(void**)&out->end, d_end, 4}},
+                             "regions", [&] { ivj_regions_free(out); }));
     out->n = total;
     return IVJ_OK;
 } IVJ_ABI_CATCH
 
 int ivj_set_stats(ivj_ctx* ctx, const ivj_side* a, const ivj_side* b, const ivj_opts* opts, int64_t bases[3], int64_t* n_intersections) try {
     if (!ctx || !bases || !n_intersections) return fail(IVJ_EINVAL, "ctx, bases or n_intersections is NULL");
-    IVJ_TRY(check_opts(opts));
-    IVJ_TRY(check_side(a, "a"));
-    IVJ_TRY(check_side(b, "b"));
+    IVJ_TRY(check_args(opts, a, "a", b, "b"));
     DeviceGuard g(ctx->device);
     SetSides s;
     IVJ_TRY(setop_sides(ctx, a, b, opts, s));
-    return set_stats_core(ctx, s.ha.ix, s.hb.ix, opts, bases, n_intersections);
+    return set_stats_core(ctx, s.a.h.ix, s.b.h.ix, opts, bases, n_intersections);
 } IVJ_ABI_CATCH
 
 // ---------------------------------------------------------------- N frames as position sets (segments, consensus)
@@ -1165,18 +1048,13 @@ void ivj_segments_free(ivj_segments* s) {
 namespace {
 // the frames of a host-path multi-frame call: uploaded and indexed (sweep only + the end order); an empty frame stays without an
 // index (ix[f] stays NULL)
-struct MultiSides {
-    std::vector<DevSide> sides;
-    std::vector<IndexHolder> holders;
-};
+using MultiSides = std::vector<FrameHost>;
 int multi_sides(ivj_ctx* ctx, const ivj_side* frames, int32_t n_frames, const ivj_opts* opts, MultiSides& s, std::vector<ivj_index*>& ix) {
-    s.sides = std::vector<DevSide>((size_t)n_frames);
-    s.holders = std::vector<IndexHolder>((size_t)n_frames);
+    s = MultiSides((size_t)n_frames);
     for (int32_t f = 0; f < n_frames; ++f) {
         if (frames[f].n == 0) continue;
-        IVJ_TRY(upload_side(ctx, &frames[f], s.sides[f]));
-        IVJ_TRY(index_build(ctx, &s.sides[f].s, opts, 3, &s.holders[f].ix));
-        ix[f] = s.holders[f].ix;
+        IVJ_TRY(upload_frame(ctx, &frames[f], opts, 3, s[f]));
+        ix[f] = s[f].h.ix;
     }
     return IVJ_OK;
 }
@@ -1202,19 +1080,8 @@ int ivj_multi_inter(ivj_ctx* ctx, const ivj_side* frames, int32_t n_frames, cons
     int64_t total = 0;
     IVJ_TRY(multi_core(ctx, ix.data(), n_frames, opts, min_frames, mode, -1, &d_contig, &d_start, &d_end, &d_mask, &own, &total));
     if (total == 0) return IVJ_OK;
-    const bool with_mask = mode == IVJ_MULTI_SEGMENTS;
-    out->contig = (int32_t*)host_result_alloc((size_t)total * 4);
-    out->start = (int32_t*)host_result_alloc((size_t)total * 4);
-    out->end = (int32_t*)host_result_alloc((size_t)total * 4);
-    if (with_mask) out->mask = (uint64_t*)host_result_alloc((size_t)total * 8);
-    if (!out->contig || !out->start || !out->end || (with_mask && !out->mask)) { ivj_segments_free(out); return fail(IVJ_ENOMEM, "host malloc(segments)"); }
-    HostXfer copy(ctx->stream, &ctx->xfer);
-    copy.d2h(out->contig, d_contig, (size_t)total * 4);
-    copy.d2h(out->start, d_start, (size_t)total * 4);
-    copy.d2h(out->end, d_end, (size_t)total * 4);
-    if (with_mask) copy.d2h(out->mask, d_mask, (size_t)total * 8);
-    const hipError_t e = copy.finish();
-    if (e != hipSuccess) { ivj_segments_free(out); return fail(IVJ_EHIP, std::string("D2H(segments): ") + hipGetErrorString(e)); }
+    IVJ_TRY(copy_out_columns(ctx, total, {{(void**)&out->contig, d_contig, 4}, {(void**)&out->start, d_start, 4}, {(void**)&out->end, d_end, 4},
+                                          {(void**)&out->mask, d_mask, 8, mode == IVJ_MULTI_SEGMENTS}}, "segments", [&] { ivj_segments_free(out); }));
     out->n = total;
     return IVJ_OK;
 } IVJ_ABI_CATCH
@@ -1240,15 +1107,14 @@ int ivj_multi_pairwise(ivj_ctx* ctx, const ivj_side* frames, int32_t n_frames, c
     IVJ_TRY(multi_sides(ctx, frames, n_frames, opts, s, ix));
     const size_t bytes = (size_t)n_frames * (size_t)n_frames * 8;
     DevBuf out;
-    hipError_t e = hipMalloc(&out.p, 2 * align_up(bytes));
-    if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(pairwise matrices): ") + hipGetErrorString(e));
+    IVJ_TRY(devbuf_alloc(out, 2 * align_up(bytes), "pairwise matrices"));
     int64_t* d_bases = (int64_t*)out.p;
     int64_t* d_runs = (int64_t*)((char*)out.p + align_up(bytes));
     IVJ_TRY(pairwise_core(ctx, ix.data(), n_frames, opts, d_bases, d_runs));
-    HostXfer copy(ctx->stream, &ctx->xfer);
+    HostXfer copy(ctx->stream, &ctx->xfer);                // (not d2h_finish: this entry words its copy failure itself)
     copy.d2h(bases, d_bases, bytes);
     copy.d2h(runs, d_runs, bytes);
-    e = copy.finish();
+    const hipError_t e = copy.finish();
     if (e != hipSuccess) return fail(IVJ_EHIP, std::string("D2H(pairwise matrices): ") + hipGetErrorString(e));
     return IVJ_OK;
 } IVJ_ABI_CATCH
@@ -1274,31 +1140,18 @@ void ivj_pieces_free(ivj_pieces* p) {
 int ivj_subtract(ivj_ctx* ctx, const ivj_side* left, const ivj_side* right, const ivj_opts* opts, ivj_pieces* out) try {
     if (!ctx || !out) return fail(IVJ_EINVAL, "ctx or out is NULL");
     std::memset(out, 0, sizeof(*out));
-    IVJ_TRY(check_opts(opts));
-    IVJ_TRY(check_side(left, "left"));
-    IVJ_TRY(check_side(right, "right"));
+    IVJ_TRY(check_args(opts, left, "left", right, "right"));
     if (left->n == 0) return IVJ_OK;
     DeviceGuard g(ctx->device);
-    DevSide dl, dr;
-    IVJ_TRY(upload_side(ctx, right, dr));
-    IVJ_TRY(upload_side(ctx, left, dl));
-    IndexHolder h;
-    IVJ_TRY(index_build(ctx, &dr.s, opts, 0, &h.ix));
+    JoinHost J;                                            // the left rows probe the index of the right ones
+    IVJ_TRY(upload_join(ctx, left, right, opts, 0, J));
     DevBuf own;
     int32_t *d_row = nullptr, *d_start = nullptr, *d_end = nullptr;
     int64_t total = 0;
-    IVJ_TRY(subtract_core(ctx, h.ix, &dl.s, opts, -1, &d_row, &d_start, &d_end, &own, &total));
+    IVJ_TRY(subtract_core(ctx, J.h.ix, &J.dp.s, opts, -1, &d_row, &d_start, &d_end, &own, &total));
     if (total == 0) return IVJ_OK;
-    out->row = (int32_t*)host_result_alloc((size_t)total * 4);
-    out->start = (int32_t*)host_result_alloc((size_t)total * 4);
-    out->end = (int32_t*)host_result_alloc((size_t)total * 4);
-    if (!out->row || !out->start || !out->end) { ivj_pieces_free(out); return fail(IVJ_ENOMEM, "host malloc(pieces)"); }
-    HostXfer copy(ctx->stream, &ctx->xfer);
-    copy.d2h(out->row, d_row, (size_t)total * 4);
-    copy.d2h(out->start, d_start, (size_t)total * 4);
-    copy.d2h(out->end, d_end, (size_t)total * 4);
-    const hipError_t e = copy.finish();
-    if (e != hipSuccess) { ivj_pieces_free(out); return fail(IVJ_EHIP, std::string("D2H(pieces): ") + hipGetErrorString(e)); }
+    IVJ_TRY(copy_out_columns(ctx, total, {{(void**)&out->row, d_row, 4}, {(void**)&out->start, d_start, 4}, {(void**)&out->end, d_end, 4}},
+                             "pieces", [&] { ivj_pieces_free(out); }));
     out->n = total;
     return IVJ_OK;
 } IVJ_ABI_CATCH
@@ -1364,11 +1217,10 @@ int ivj_take(ivj_ctx* ctx, const int32_t* idx, int64_t n, int32_t n_cols, const 
     DeviceGuard g(ctx->device);
     const size_t words = (size_t)((n + 63) / 64);
     DevBuf d_idx, d_src, d_dst, d_val;
-    hipError_t e = hipMalloc(&d_idx.p, (size_t)n * 4);
-    if (e == hipSuccess) e = hipMalloc(&d_src.p, max_src ? max_src : 16);
-    if (e == hipSuccess) e = hipMalloc(&d_dst.p, max_dst);
-    if (e == hipSuccess && any_valid) e = hipMalloc(&d_val.p, words * 8);
-    if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(take): ") + hipGetErrorString(e));
+    IVJ_TRY(devbuf_alloc(d_idx, (size_t)n * 4, "take"));
+    IVJ_TRY(devbuf_alloc(d_src, max_src ? max_src : 16, "take"));
+    IVJ_TRY(devbuf_alloc(d_dst, max_dst, "take"));
+    if (any_valid) IVJ_TRY(devbuf_alloc(d_val, words * 8, "take"));
     HostXfer copy(ctx->stream, &ctx->xfer);
     copy.h2d(d_idx.p, idx, (size_t)n * 4);
     for (int c = 0; c < n_cols; ++c) {
@@ -1397,31 +1249,25 @@ void ivj_rows_free(ivj_rows* r) {
 int ivj_overlap_rows(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, ivj_rows* out) try {
     if (!ctx || !out) return fail(IVJ_EINVAL, "ctx or out is NULL");
     std::memset(out, 0, sizeof(*out));
-    IVJ_TRY(check_opts(opts));
-    IVJ_TRY(check_side(probe, "probe"));
-    IVJ_TRY(check_side(build, "build"));
+    IVJ_TRY(check_args(opts, probe, "probe", build, "build"));
     if (probe->row_id || build->row_id) return fail(IVJ_EINVAL, "ivj_overlap_rows gathers by position: row_id must be NULL");
     DeviceGuard g(ctx->device);
-    DevSide dp, db;
-    IVJ_TRY(upload_side(ctx, build, db));
-    IVJ_TRY(upload_side(ctx, probe, dp));
-    IndexHolder h;
-    IVJ_TRY(index_build(ctx, &db.s, opts, 0, &h.ix));
+    JoinHost J;
+    IVJ_TRY(upload_join(ctx, probe, build, opts, 0, J));
     int64_t total = 0;
-    IVJ_TRY(overlap_count(ctx, h.ix, &dp.s, opts, &total));
+    IVJ_TRY(overlap_count(ctx, J.h.ix, &J.dp.s, opts, &total));
     if (total == 0) return IVJ_OK;
     if (!host_result_fits((size_t)total * 28))
         return fail(IVJ_ENOMEM, "the result (" + std::to_string(total) + " rows x 7 columns) does not fit the available host memory");
     DevBuf cols;                                            // 7 columns in one allocation
     const size_t col = align_up((size_t)total * 4);
-    hipError_t e = hipMalloc(&cols.p, 7 * col);
-    if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(rows): ") + hipGetErrorString(e));
+    IVJ_TRY(devbuf_alloc(cols, 7 * col, "rows"));
     ivj_rows d;
     d.n_pairs = total;
     int32_t** dcols[7] = {&d.probe_idx, &d.build_idx, &d.contig, &d.start_1, &d.end_1, &d.start_2, &d.end_2};
     for (int k = 0; k < 7; ++k) *dcols[k] = (int32_t*)((char*)cols.p + k * col);
-    IVJ_TRY(overlap_fill(ctx, h.ix, &dp.s, opts, d.probe_idx, d.build_idx, total));
-    IVJ_TRY(ivj_materialize_dev(ctx, &dp.s, &db.s, &d));
+    IVJ_TRY(overlap_fill(ctx, J.h.ix, &J.dp.s, opts, d.probe_idx, d.build_idx, total));
+    IVJ_TRY(ivj_materialize_dev(ctx, &J.dp.s, &J.db.s, &d));
     int32_t** hcols[7] = {&out->probe_idx, &out->build_idx, &out->contig, &out->start_1, &out->end_1, &out->start_2, &out->end_2};
     HostXfer copy(ctx->stream, &ctx->xfer);
     for (int k = 0; k < 7; ++k) {
@@ -1445,25 +1291,16 @@ void ivj_pairs_free(ivj_pairs* p) {
 
 int ivj_count_overlaps(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, int64_t* counts) try {
     if (!ctx) return fail(IVJ_EINVAL, "ctx is NULL");
-    IVJ_TRY(check_opts(opts));
-    IVJ_TRY(check_side(probe, "probe"));
-    IVJ_TRY(check_side(build, "build"));
+    IVJ_TRY(check_args(opts, probe, "probe", build, "build"));
     if (probe->n == 0) return IVJ_OK;
     if (!counts) return fail(IVJ_EINVAL, "counts is NULL");
     DeviceGuard g(ctx->device);
-    DevSide dp, db;
-    IVJ_TRY(upload_side(ctx, build, db));
-    IVJ_TRY(upload_side(ctx, probe, dp));
-    IndexHolder h;
-    IVJ_TRY(index_build(ctx, &db.s, opts, 1, &h.ix));
+    JoinHost J;
+    IVJ_TRY(upload_join(ctx, probe, build, opts, 1, J));
     DevBuf dc;
-    hipError_t e = hipMalloc(&dc.p, (size_t)probe->n * 8);
-    if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(counts): ") + hipGetErrorString(e));
-    IVJ_TRY(count_overlaps_dev(ctx, h.ix, &dp.s, opts, (int64_t*)dc.p));
-    HostXfer copy(ctx->stream, &ctx->xfer);
-    copy.d2h(counts, dc.p, (size_t)probe->n * 8);
-    HIP_TRY(copy.finish());
-    return IVJ_OK;
+    IVJ_TRY(devbuf_alloc(dc, (size_t)probe->n * 8, "counts"));
+    IVJ_TRY(count_overlaps_dev(ctx, J.h.ix, &J.dp.s, opts, (int64_t*)dc.p));
+    return d2h_finish(ctx, {{counts, dc.p, (size_t)probe->n * 8}});
 } IVJ_ABI_CATCH
 
 // ---------------------------------------------------------------- overlap thresholds (thresh.hip.h, host_thresh.hip.h)
@@ -1495,9 +1332,7 @@ int ivj_overlap_thresh(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* buil
                        ivj_pairs* out) try {
     if (!ctx || !out) return fail(IVJ_EINVAL, "ctx or out is NULL");
     out->n_pairs = 0; out->probe_idx = nullptr; out->build_idx = nullptr;
-    IVJ_TRY(check_opts(opts));
-    IVJ_TRY(check_side(probe, "probe"));
-    IVJ_TRY(check_side(build, "build"));
+    IVJ_TRY(check_args(opts, probe, "probe", build, "build"));
     IVJ_TRY(check_thresholds(thr));
     DeviceGuard g(ctx->device);
     ThreshHost H;
@@ -1506,31 +1341,16 @@ int ivj_overlap_thresh(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* buil
     int64_t total = 0;
     IVJ_TRY(thresh_count(ctx, H.h.ix, &H.dp.s, opts, &H.dthr, nullptr, true, plan, &total));
     if (total == 0) return IVJ_OK;
-    if (!host_result_fits((size_t)total * 8))
-        return fail(IVJ_ENOMEM, "the result (" + std::to_string(total) + " pairs, " + std::to_string((size_t)total * 8 >> 20) + " MiB) does not fit the available host memory; use ivj_overlap_thresh_dev");
-    DevBuf op, ob;
-    hipError_t e = hipMalloc(&op.p, (size_t)total * 4);
-    if (e == hipSuccess) e = hipMalloc(&ob.p, (size_t)total * 4);
-    if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(pairs): ") + hipGetErrorString(e));
-    IVJ_TRY(thresh_emit(ctx, H.h.ix, plan, (int32_t*)op.p, (int32_t*)ob.p));
-    out->probe_idx = (int32_t*)host_result_alloc((size_t)total * 4);
-    out->build_idx = (int32_t*)host_result_alloc((size_t)total * 4);
-    if (!out->probe_idx || !out->build_idx) { ivj_pairs_free(out); return fail(IVJ_ENOMEM, "host malloc(pairs)"); }
-    HostXfer copy(ctx->stream, &ctx->xfer);
-    copy.d2h(out->probe_idx, op.p, (size_t)total * 4);
-    copy.d2h(out->build_idx, ob.p, (size_t)total * 4);
-    const hipError_t ce = copy.finish();
-    if (ce != hipSuccess) { ivj_pairs_free(out); return fail(IVJ_EHIP, std::string("D2H(pairs): ") + hipGetErrorString(ce)); }
-    out->n_pairs = total;
-    return IVJ_OK;
+    DevPairs P;
+    IVJ_TRY(alloc_pairs(total, 8, "; use ivj_overlap_thresh_dev", P));
+    IVJ_TRY(thresh_emit(ctx, H.h.ix, plan, (int32_t*)P.p.p, (int32_t*)P.b.p));
+    return pairs_to_host(ctx, total, P, out);
 } IVJ_ABI_CATCH
 
 int ivj_count_overlaps_thresh(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, const ivj_thresholds* thr,
                               int64_t* counts) try {
     if (!ctx) return fail(IVJ_EINVAL, "ctx is NULL");
-    IVJ_TRY(check_opts(opts));
-    IVJ_TRY(check_side(probe, "probe"));
-    IVJ_TRY(check_side(build, "build"));
+    IVJ_TRY(check_args(opts, probe, "probe", build, "build"));
     IVJ_TRY(check_thresholds(thr));
     if (probe->n == 0) return IVJ_OK;
     if (!counts) return fail(IVJ_EINVAL, "counts is NULL");
@@ -1538,14 +1358,10 @@ int ivj_count_overlaps_thresh(ivj_ctx* ctx, const ivj_side* probe, const ivj_sid
     ThreshHost H;
     IVJ_TRY(thresh_upload(ctx, probe, build, opts, thr, H));
     DevBuf dc;
-    hipError_t e = hipMalloc(&dc.p, (size_t)probe->n * 8);
-    if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(counts): ") + hipGetErrorString(e));
+    IVJ_TRY(devbuf_alloc(dc, (size_t)probe->n * 8, "counts"));
     ThreshPlan plan;
     IVJ_TRY(thresh_count(ctx, H.h.ix, &H.dp.s, opts, &H.dthr, (int64_t*)dc.p, false, plan, nullptr));
-    HostXfer copy(ctx->stream, &ctx->xfer);
-    copy.d2h(counts, dc.p, (size_t)probe->n * 8);
-    HIP_TRY(copy.finish());
-    return IVJ_OK;
+    return d2h_finish(ctx, {{counts, dc.p, (size_t)probe->n * 8}});
 } IVJ_ABI_CATCH
 
 // ---------------------------------------------------------------- distance window (window.hip.h, host_window.hip.h)
@@ -1580,9 +1396,7 @@ int ivj_overlap_window(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* buil
     if (!ctx || !out) return fail(IVJ_EINVAL, "ctx or out is NULL");
     out->n_pairs = 0; out->probe_idx = nullptr; out->build_idx = nullptr;
     if (dist) *dist = nullptr;
-    IVJ_TRY(check_opts(opts));
-    IVJ_TRY(check_side(probe, "probe"));
-    IVJ_TRY(check_side(build, "build"));
+    IVJ_TRY(check_args(opts, probe, "probe", build, "build"));
     IVJ_TRY(check_window(win));
     DeviceGuard g(ctx->device);
     WindowHost H;
@@ -1591,36 +1405,16 @@ int ivj_overlap_window(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* buil
     int64_t total = 0;
     IVJ_TRY(window_count(ctx, H.h.ix, &H.dp.s, opts, &H.dwin, nullptr, true, plan, &total));
     if (total == 0) return IVJ_OK;
-    const size_t pair_bytes = dist ? 16 : 8;
-    if (!host_result_fits((size_t)total * pair_bytes))
-        return fail(IVJ_ENOMEM, "the result (" + std::to_string(total) + " pairs, " + std::to_string((size_t)total * pair_bytes >> 20) + " MiB) does not fit the available host memory; use ivj_overlap_window_dev");
-    DevBuf op, ob, od;
-    hipError_t e = hipMalloc(&op.p, (size_t)total * 4);
-    if (e == hipSuccess) e = hipMalloc(&ob.p, (size_t)total * 4);
-    if (e == hipSuccess && dist) e = hipMalloc(&od.p, (size_t)total * 8);
-    if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(pairs): ") + hipGetErrorString(e));
-    IVJ_TRY(window_emit(ctx, H.h.ix, plan, (int32_t*)op.p, (int32_t*)ob.p, (int64_t*)od.p));
-    auto drop = [&] { ivj_pairs_free(out); if (dist) { std::free(*dist); *dist = nullptr; } };
-    out->probe_idx = (int32_t*)host_result_alloc((size_t)total * 4);
-    out->build_idx = (int32_t*)host_result_alloc((size_t)total * 4);
-    if (dist) *dist = (int64_t*)host_result_alloc((size_t)total * 8);
-    if (!out->probe_idx || !out->build_idx || (dist && !*dist)) { drop(); return fail(IVJ_ENOMEM, "host malloc(pairs)"); }
-    HostXfer copy(ctx->stream, &ctx->xfer);
-    copy.d2h(out->probe_idx, op.p, (size_t)total * 4);
-    copy.d2h(out->build_idx, ob.p, (size_t)total * 4);
-    if (dist) copy.d2h(*dist, od.p, (size_t)total * 8);
-    const hipError_t ce = copy.finish();
-    if (ce != hipSuccess) { drop(); return fail(IVJ_EHIP, std::string("D2H(pairs): ") + hipGetErrorString(ce)); }
-    out->n_pairs = total;
-    return IVJ_OK;
+    DevPairs P;
+    IVJ_TRY(alloc_pairs(total, dist ? 16 : 8, "; use ivj_overlap_window_dev", P));
+    IVJ_TRY(window_emit(ctx, H.h.ix, plan, (int32_t*)P.p.p, (int32_t*)P.b.p, (int64_t*)P.d.p));
+    return pairs_to_host(ctx, total, P, out, dist);
 } IVJ_ABI_CATCH
 
 int ivj_count_window(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, const ivj_window* win,
                      int64_t* counts) try {
     if (!ctx) return fail(IVJ_EINVAL, "ctx is NULL");
-    IVJ_TRY(check_opts(opts));
-    IVJ_TRY(check_side(probe, "probe"));
-    IVJ_TRY(check_side(build, "build"));
+    IVJ_TRY(check_args(opts, probe, "probe", build, "build"));
     IVJ_TRY(check_window(win));
     if (probe->n == 0) return IVJ_OK;
     if (!counts) return fail(IVJ_EINVAL, "counts is NULL");
@@ -1628,14 +1422,10 @@ int ivj_count_window(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build,
     WindowHost H;
     IVJ_TRY(window_upload(ctx, probe, build, opts, win, H));
     DevBuf dc;
-    hipError_t e = hipMalloc(&dc.p, (size_t)probe->n * 8);
-    if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(counts): ") + hipGetErrorString(e));
+    IVJ_TRY(devbuf_alloc(dc, (size_t)probe->n * 8, "counts"));
     WindowPlan plan;
     IVJ_TRY(window_count(ctx, H.h.ix, &H.dp.s, opts, &H.dwin, (int64_t*)dc.p, false, plan, nullptr));
-    HostXfer copy(ctx->stream, &ctx->xfer);
-    copy.d2h(counts, dc.p, (size_t)probe->n * 8);
-    HIP_TRY(copy.finish());
-    return IVJ_OK;
+    return d2h_finish(ctx, {{counts, dc.p, (size_t)probe->n * 8}});
 } IVJ_ABI_CATCH
 
 // ---------------------------------------------------------------- join kinds: semi, anti, left outer (select.hip.h, host_select.hip.h)
@@ -1663,9 +1453,7 @@ int ivj_overlap_select(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* buil
                        int32_t mode, ivj_rowsel* out) try {
     if (!ctx || !out) return fail(IVJ_EINVAL, "ctx or out is NULL");
     out->rows = nullptr; out->n = 0;
-    IVJ_TRY(check_opts(opts));
-    IVJ_TRY(check_side(probe, "probe"));
-    IVJ_TRY(check_side(build, "build"));
+    IVJ_TRY(check_args(opts, probe, "probe", build, "build"));
     if (thr) IVJ_TRY(check_thresholds(thr));
     IVJ_TRY(check_select_mode(mode));
     if (probe->n == 0) return IVJ_OK;
@@ -1677,15 +1465,9 @@ int ivj_overlap_select(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* buil
     IVJ_TRY(select_count(ctx, U.H.h.ix, &U.H.dp.s, opts, U.dthr, mode, S, &total));
     if (total == 0) return IVJ_OK;
     DevBuf rows;
-    hipError_t e = hipMalloc(&rows.p, (size_t)total * 4);
-    if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(rows): ") + hipGetErrorString(e));
+    IVJ_TRY(devbuf_alloc(rows, (size_t)total * 4, "rows"));
     IVJ_TRY(select_emit(ctx, S, (int32_t*)rows.p, nullptr));
-    out->rows = (int32_t*)host_result_alloc((size_t)total * 4);
-    if (!out->rows) return fail(IVJ_ENOMEM, "host malloc(rows)");
-    HostXfer copy(ctx->stream, &ctx->xfer);
-    copy.d2h(out->rows, rows.p, (size_t)total * 4);
-    const hipError_t ce = copy.finish();
-    if (ce != hipSuccess) { ivj_rowsel_free(out); return fail(IVJ_EHIP, std::string("D2H(rows): ") + hipGetErrorString(ce)); }
+    IVJ_TRY(copy_out_columns(ctx, total, {{(void**)&out->rows, rows.p, 4}}, "rows", [&] { ivj_rowsel_free(out); }));
     out->n = total;
     return IVJ_OK;
 } IVJ_ABI_CATCH
@@ -1694,9 +1476,7 @@ int ivj_overlap_outer(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build
                       ivj_pairs* out) try {
     if (!ctx || !out) return fail(IVJ_EINVAL, "ctx or out is NULL");
     out->n_pairs = 0; out->probe_idx = nullptr; out->build_idx = nullptr;
-    IVJ_TRY(check_opts(opts));
-    IVJ_TRY(check_side(probe, "probe"));
-    IVJ_TRY(check_side(build, "build"));
+    IVJ_TRY(check_args(opts, probe, "probe", build, "build"));
     if (thr) IVJ_TRY(check_thresholds(thr));
     if (probe->n == 0) return IVJ_OK;
     DeviceGuard g(ctx->device);
@@ -1715,27 +1495,15 @@ int ivj_overlap_outer(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build
     }
     const int64_t total = n_inner + n_anti;
     if (total == 0) return IVJ_OK;
-    if (!host_result_fits((size_t)total * 8))
-        return fail(IVJ_ENOMEM, "the result (" + std::to_string(total) + " pairs, " + std::to_string((size_t)total * 8 >> 20) + " MiB) does not fit the available host memory");
-    DevBuf op, ob;
-    hipError_t e = hipMalloc(&op.p, (size_t)total * 4);
-    if (e == hipSuccess) e = hipMalloc(&ob.p, (size_t)total * 4);
-    if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(pairs): ") + hipGetErrorString(e));
+    DevPairs P;
+    IVJ_TRY(alloc_pairs(total, 8, "", P));
+    int32_t *op = (int32_t*)P.p.p, *ob = (int32_t*)P.b.p;
     if (n_inner > 0) {
-        if (thr) IVJ_TRY(thresh_emit(ctx, ix, plan, (int32_t*)op.p, (int32_t*)ob.p));
-        else IVJ_TRY(overlap_fill(ctx, ix, dp, opts, (int32_t*)op.p, (int32_t*)ob.p, n_inner));
+        if (thr) IVJ_TRY(thresh_emit(ctx, ix, plan, op, ob));
+        else IVJ_TRY(overlap_fill(ctx, ix, dp, opts, op, ob, n_inner));
     }
-    if (n_anti > 0) IVJ_TRY(select_emit(ctx, S, (int32_t*)op.p + n_inner, (int32_t*)ob.p + n_inner));
-    out->probe_idx = (int32_t*)host_result_alloc((size_t)total * 4);
-    out->build_idx = (int32_t*)host_result_alloc((size_t)total * 4);
-    if (!out->probe_idx || !out->build_idx) { ivj_pairs_free(out); return fail(IVJ_ENOMEM, "host malloc(pairs)"); }
-    HostXfer copy(ctx->stream, &ctx->xfer);
-    copy.d2h(out->probe_idx, op.p, (size_t)total * 4);
-    copy.d2h(out->build_idx, ob.p, (size_t)total * 4);
-    const hipError_t ce = copy.finish();
-    if (ce != hipSuccess) { ivj_pairs_free(out); return fail(IVJ_EHIP, std::string("D2H(pairs): ") + hipGetErrorString(ce)); }
-    out->n_pairs = total;
-    return IVJ_OK;
+    if (n_anti > 0) IVJ_TRY(select_emit(ctx, S, op + n_inner, ob + n_inner));
+    return pairs_to_host(ctx, total, P, out);
 } IVJ_ABI_CATCH
 
 // ---------------------------------------------------------------- map_overlaps: build-side aggregates per probe row (overlap_agg.hip.h)
@@ -1855,21 +1623,17 @@ int ivj_permute_overlaps(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* bu
         return IVJ_OK;
     }
     DeviceGuard g(ctx->device);
-    DevSide dp, db;
-    IVJ_TRY(upload_side(ctx, build, db));
-    IVJ_TRY(upload_side(ctx, probe, dp));
-    IndexHolder h;
-    IVJ_TRY(index_build(ctx, &db.s, opts, 1, &h.ix));
+    JoinHost J;
+    IVJ_TRY(upload_join(ctx, probe, build, opts, 1, J));
     PermPlan P;
-    IVJ_TRY(permute_plan(ctx, h.ix, &dp.s, opts, n_perm, P));
+    IVJ_TRY(permute_plan(ctx, J.h.ix, &J.dp.s, opts, n_perm, P));
     // the offsets travel in pieces of whole permutations (n_perm x n_contigs may be far more than one allocation should hold)
     const size_t row_bytes = nc * 4;
     int64_t rows_per_piece = (int64_t)(((size_t)64 << 20) / row_bytes);
     rows_per_piece = rows_per_piece < 1 ? 1 : (rows_per_piece > n_perm ? n_perm : rows_per_piece);
     const size_t len_bytes = align_up(row_bytes), out_bytes = align_up((size_t)n_perm * 8), piece_bytes = align_up((size_t)rows_per_piece * row_bytes);
     DevBuf buf;
-    hipError_t e = hipMalloc(&buf.p, len_bytes + 2 * out_bytes + piece_bytes);
-    if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(permutation tables): ") + hipGetErrorString(e));
+    IVJ_TRY(devbuf_alloc(buf, len_bytes + 2 * out_bytes + piece_bytes, "permutation tables"));
     int32_t* d_len = (int32_t*)buf.p;
     int64_t* d_pairs = (int64_t*)((char*)buf.p + len_bytes);
     int64_t* d_rows = (int64_t*)((char*)buf.p + len_bytes + out_bytes);
@@ -1880,7 +1644,7 @@ int ivj_permute_overlaps(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* bu
         // the copies and the launches are ordered by the stream: piece k + 1 overwrites the buffer after piece k's launches ran
         const int64_t np = (n_perm - p0) < rows_per_piece ? (n_perm - p0) : rows_per_piece;
         copy.h2d(d_off, offsets + (size_t)p0 * nc, (size_t)np * row_bytes);
-        IVJ_TRY(permute_run(ctx, h.ix, P, d_len, d_off, np, d_pairs + p0, d_rows + p0));
+        IVJ_TRY(permute_run(ctx, J.h.ix, P, d_len, d_off, np, d_pairs + p0, d_rows + p0));
     }
     copy.d2h(n_pairs, d_pairs, (size_t)n_perm * 8);
     copy.d2h(n_rows, d_rows, (size_t)n_perm * 8);
@@ -1891,33 +1655,22 @@ int ivj_permute_overlaps(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* bu
 int ivj_nearest(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, int32_t* idx, int64_t* dist,
                 int32_t* n_found) try {
     if (!ctx) return fail(IVJ_EINVAL, "ctx is NULL");
-    IVJ_TRY(check_opts(opts));
-    IVJ_TRY(check_side(probe, "probe"));
-    IVJ_TRY(check_side(build, "build"));
+    IVJ_TRY(check_args(opts, probe, "probe", build, "build"));
     if (probe->n == 0) return IVJ_OK;
     if (!idx || !dist || !n_found) return fail(IVJ_EINVAL, "nearest output buffers are NULL");
     const int k = opts->nearest_k < 1 ? 1 : opts->nearest_k;
     if (k > 1024) return fail(IVJ_EINVAL, "nearest_k > 1024");
     DeviceGuard g(ctx->device);
-    DevSide dp, db;
-    IVJ_TRY(upload_side(ctx, build, db));
-    IVJ_TRY(upload_side(ctx, probe, dp));
-    IndexHolder h;
+    JoinHost J;
     const bool general = !(k == 1 && opts->include_overlaps);
-    IVJ_TRY(index_build(ctx, &db.s, opts, general ? 1 : 0, &h.ix));
+    IVJ_TRY(upload_join(ctx, probe, build, opts, general ? 1 : 0, J));
     const size_t slots = (size_t)probe->n * (size_t)k;
     DevBuf di, dd, dn;
-    hipError_t e = hipMalloc(&di.p, slots * 4);
-    if (e == hipSuccess) e = hipMalloc(&dd.p, slots * 8);
-    if (e == hipSuccess) e = hipMalloc(&dn.p, (size_t)probe->n * 4);
-    if (e != hipSuccess) return fail(IVJ_ENOMEM, std::string("hipMalloc(nearest): ") + hipGetErrorString(e));
-    IVJ_TRY(nearest_dev(ctx, h.ix, &dp.s, opts, (int32_t*)di.p, (int64_t*)dd.p, (int32_t*)dn.p));
-    HostXfer copy(ctx->stream, &ctx->xfer);
-    copy.d2h(idx, di.p, slots * 4);
-    copy.d2h(dist, dd.p, slots * 8);
-    copy.d2h(n_found, dn.p, (size_t)probe->n * 4);
-    HIP_TRY(copy.finish());
-    return IVJ_OK;
+    IVJ_TRY(devbuf_alloc(di, slots * 4, "nearest"));
+    IVJ_TRY(devbuf_alloc(dd, slots * 8, "nearest"));
+    IVJ_TRY(devbuf_alloc(dn, (size_t)probe->n * 4, "nearest"));
+    IVJ_TRY(nearest_dev(ctx, J.h.ix, &J.dp.s, opts, (int32_t*)di.p, (int64_t*)dd.p, (int32_t*)dn.p));
+    return d2h_finish(ctx, {{idx, di.p, slots * 4}, {dist, dd.p, slots * 8}, {n_found, dn.p, (size_t)probe->n * 4}});
 } IVJ_ABI_CATCH
 
 // ---------------------------------------------------------------- streaming probe session

@@ -600,6 +600,60 @@ def _owned_view(ptr, n, owner) -> np.ndarray:
     return np.frombuffer(buf, dtype=np.int32)
 
 
+# ---- what the host-buffer methods of Engine share: sides in, columns out ----
+
+def _host_sides(a, b):
+    """Both sides of a two-sided host call -> (ivj_side of a, ivj_side of b, the arrays they point into: keep them until the
+    call returned)."""
+    sa, keep_a = _host_side(*a)
+    sb, keep_b = _host_side(*b)
+    return sa, sb, (keep_a, keep_b)
+
+
+def _frames(frames):
+    """The frames of a multi-frame host call -> (ivj_side array, keep-alive)."""
+    sides = (_Side * len(frames))()
+    keep = []
+    for f, frame in enumerate(frames):
+        sides[f], arrays = _host_side(*frame)
+        keep.append(arrays)
+    return sides, keep
+
+
+def _reverse_flags(reverse, n: int):
+    """The ``reverse`` argument of the profile calls as contiguous uint8 flags, one per window, or None."""
+    if reverse is None:
+        return None
+    rev = np.ascontiguousarray(np.asarray(reverse).astype(bool).astype(np.uint8))
+    if rev.shape != (n,):
+        raise ValueError(f"reverse must hold one flag per window ({n}), got shape {rev.shape}")
+    return rev
+
+
+def _agg_in(values, valid, ops, n: int):
+    """One (values, valid, ops) value column of ``n`` rows -> (its ivj_agg_in, the checked values array, keep-alive)."""
+    values, valid, ops = _agg_column(values, valid, ops, n)
+    col = _AggIn(values.ctypes.data if n else None, valid.ctypes.data if valid is not None and n else None,
+                 AGG_I64 if values.dtype == np.int64 else AGG_F64, ops)
+    return col, values, (values, valid)
+
+
+def _copy_columns(out, names, dtypes, free=None):
+    """The named columns of a library-allocated result struct (``out.n`` rows) as numpy copies -- empty arrays of ``dtypes`` when
+    it has no rows -- after which ``free(pointer to out)`` releases the struct, whatever happened."""
+    try:
+        n = out.n
+        return tuple(np.ctypeslib.as_array(getattr(out, name), shape=(n,)).copy() if n else np.empty(0, dtype)
+                     for name, dtype in zip(names, dtypes))
+    finally:
+        if free is not None:
+            free(C.byref(out))
+
+
+_I32x3 = (np.int32,) * 3
+_MERGED_COLUMNS, _MERGED_DTYPES = ("contig", "start", "end", "n_intervals"), _I32x3 + (np.int64,)
+
+
 class ProbeStream:
     """Streaming probe session (ivj_stream_*): the build side is indexed once, probe batches are submitted one at a time;
     every submit overlaps the H2D copy of its batch, the join of the previous batch and the D2H copy of the one before.
@@ -733,26 +787,28 @@ class Engine:
             pass
 
     # ---- host-buffer entry points (numpy in, numpy out) --------------------
+    def _pairs_result(self, out: _Pairs):
+        """An ivj_pairs result -> (probe_idx, build_idx).  No copy: the arrays view the library's (pre-faulted, huge-page) result
+        buffers, which are freed when the last view of either array is gone."""
+        n = out.n_pairs
+        if n == 0:
+            self.L.ivj_pairs_free(C.byref(out))
+            return np.empty(0, np.int32), np.empty(0, np.int32)
+        owner = _PairsOwner(load_library(), out)
+        return _owned_view(out.probe_idx, n, owner), _owned_view(out.build_idx, n, owner)
+
     def overlap(self, probe, build, strict: bool, n_contigs: int, partition_mode: int = 0, table_mode: int = 0, slice_rows: int = 0,
                 slice_chunk: int = 0, deterministic: bool = False):
         """probe/build: (contig_id, start, end) int32 arrays -> (probe_idx, build_idx).
         partition_mode: 0 auto, 1 256 buckets + window scan, 2 never (pairs then come in probe-row order), 6 index slices in LDS.
         deterministic: the slice path's output is identical from run to run (stable partition; ivj_opts.deterministic)."""
-        ps, keep_p = _host_side(*probe)
-        bs, keep_b = _host_side(*build)
+        ps, bs, keep = _host_sides(probe, build)
         o = make_opts(strict, n_contigs, partition_mode=partition_mode, table_mode=table_mode, slice_rows=slice_rows, slice_chunk=slice_chunk,
                       deterministic=deterministic)
         out = _Pairs()
         _check(self.L, self.L.ivj_overlap(self.h, C.byref(ps), C.byref(bs), C.byref(o), C.byref(out)), "ivj_overlap")
-        del keep_p, keep_b
-        n = out.n_pairs
-        if n == 0:
-            self.L.ivj_pairs_free(C.byref(out))
-            return np.empty(0, np.int32), np.empty(0, np.int32)
-        # no copy: the arrays view the library's (pre-faulted, huge-page) result buffers, which are freed when the last
-        # view of either array is gone
-        owner = _PairsOwner(load_library(), out)
-        return _owned_view(out.probe_idx, n, owner), _owned_view(out.build_idx, n, owner)
+        del keep
+        return self._pairs_result(out)
 
     def take_columns(self, idx: np.ndarray, columns, nullable: bool = False):
         """Arrow ``take`` of fixed-width host columns through HBM (ivj_take): ``columns`` = numpy arrays of 4- or 8-byte
@@ -782,12 +838,11 @@ class Engine:
         columns of both sides for every pair.  -> dict of int32 numpy arrays keyed by ROW_COLUMNS, or
         (as_arrow=True) a pyarrow.RecordBatch that owns the library's host buffers through the Arrow C
         Data interface (ivj_rows_export_arrow; no copy)."""
-        ps, keep_p = _host_side(*probe)
-        bs, keep_b = _host_side(*build)
+        ps, bs, keep = _host_sides(probe, build)
         o = make_opts(strict, n_contigs, partition_mode=partition_mode)
         out = _Rows()
         _check(self.L, self.L.ivj_overlap_rows(self.h, C.byref(ps), C.byref(bs), C.byref(o), C.byref(out)), "ivj_overlap_rows")
-        del keep_p, keep_b
+        del keep
         try:
             if as_arrow:
                 import pyarrow as pa
@@ -809,14 +864,7 @@ class Engine:
         out = _Merged()
         _check(self.L, self.L.ivj_merge(self.h, C.byref(fs), C.byref(o), int(min_dist), C.byref(out)), "ivj_merge")
         del keep
-        try:
-            n = out.n
-            if n == 0:
-                return np.empty(0, np.int32), np.empty(0, np.int32), np.empty(0, np.int32), np.empty(0, np.int64)
-            return (np.ctypeslib.as_array(out.contig, shape=(n,)).copy(), np.ctypeslib.as_array(out.start, shape=(n,)).copy(),
-                    np.ctypeslib.as_array(out.end, shape=(n,)).copy(), np.ctypeslib.as_array(out.n_intervals, shape=(n,)).copy())
-        finally:
-            self.L.ivj_merged_free(C.byref(out))
+        return _copy_columns(out, _MERGED_COLUMNS, _MERGED_DTYPES, self.L.ivj_merged_free)
 
     def merge_agg(self, frame, strict: bool, n_contigs: int, agg, min_dist: int = 0):
         """pb.merge(agg=...): ``agg`` = a list of (values, valid, ops) per value column -- values an int64 or float64 array with
@@ -831,11 +879,9 @@ class Engine:
         outs = (_AggOut * max(len(agg), 1))()
         dtypes = []
         for k, (values, valid, ops) in enumerate(agg):
-            values, valid, ops = _agg_column(values, valid, ops, fs.n)
-            keep += (values, valid)
+            cols[k], values, arrays = _agg_in(values, valid, ops, fs.n)
+            keep += arrays
             dtypes.append(values.dtype)
-            cols[k] = _AggIn(values.ctypes.data if fs.n else None, valid.ctypes.data if valid is not None and fs.n else None,
-                             AGG_I64 if values.dtype == np.int64 else AGG_F64, ops)
         out = _Merged()
         _check(self.L, self.L.ivj_merge_agg(self.h, C.byref(fs), C.byref(o), int(min_dist), len(agg), cols, C.byref(out), outs), "ivj_merge_agg")
         del keep
@@ -847,11 +893,7 @@ class Engine:
                     return np.empty(0, dtype)
                 return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_int64)), shape=(n,)).view(dtype).copy()
 
-            if n == 0:
-                table = (np.empty(0, np.int32), np.empty(0, np.int32), np.empty(0, np.int32), np.empty(0, np.int64))
-            else:
-                table = (np.ctypeslib.as_array(out.contig, shape=(n,)).copy(), np.ctypeslib.as_array(out.start, shape=(n,)).copy(),
-                         np.ctypeslib.as_array(out.end, shape=(n,)).copy(), np.ctypeslib.as_array(out.n_intervals, shape=(n,)).copy())
+            table = _copy_columns(out, _MERGED_COLUMNS, _MERGED_DTYPES)      # (freed below, with the aggregates)
             results = []
             for k in range(len(agg)):
                 kinds = {"sum": dtypes[k], "min": dtypes[k], "max": dtypes[k], "mean": np.float64, "count": np.int64}
@@ -868,42 +910,28 @@ class Engine:
         out = _Blocks()
         _check(self.L, self.L.ivj_depth(self.h, C.byref(fs), C.byref(o), C.byref(out)), "ivj_depth")
         del keep
-        try:
-            n = out.n
-            if n == 0:
-                return tuple(np.empty(0, np.int32) for _ in range(4))
-            return tuple(np.ctypeslib.as_array(getattr(out, name), shape=(n,)).copy() for name in ("contig", "start", "end", "depth"))
-        finally:
-            self.L.ivj_blocks_free(C.byref(out))
+        return _copy_columns(out, ("contig", "start", "end", "depth"), (np.int32,) * 4, self.L.ivj_blocks_free)
 
     def setop(self, a, b, op, strict: bool, n_contigs: int):
         """pb.set_intersect / set_union / set_difference / set_symmetric_difference: -> (contig id, start, end) int32 arrays of
         the maximal runs of op(U(a), U(b)), (contig id, start) order, bounds in the mode's own convention.  ``op``: a name of
         SETOPS or its number."""
-        sa, keep_a = _host_side(*a)
-        sb, keep_b = _host_side(*b)
+        sa, sb, keep = _host_sides(a, b)
         o = make_opts(strict, n_contigs)
         out = _Regions()
         _check(self.L, self.L.ivj_setop(self.h, C.byref(sa), C.byref(sb), C.byref(o), _setop_code(op), C.byref(out)), "ivj_setop")
-        del keep_a, keep_b
-        try:
-            n = out.n
-            if n == 0:
-                return tuple(np.empty(0, np.int32) for _ in range(3))
-            return tuple(np.ctypeslib.as_array(getattr(out, name), shape=(n,)).copy() for name in ("contig", "start", "end"))
-        finally:
-            self.L.ivj_regions_free(C.byref(out))
+        del keep
+        return _copy_columns(out, ("contig", "start", "end"), _I32x3, self.L.ivj_regions_free)
 
     def set_stats(self, a, b, strict: bool, n_contigs: int):
         """-> (only_a, only_b, both, n_intersections): the positions only U(a), only U(b), both cover (exact ints) and the
         number of regions of the intersection, from one walk."""
-        sa, keep_a = _host_side(*a)
-        sb, keep_b = _host_side(*b)
+        sa, sb, keep = _host_sides(a, b)
         o = make_opts(strict, n_contigs)
         bases = (C.c_int64 * 3)()
         ni = C.c_int64(0)
         _check(self.L, self.L.ivj_set_stats(self.h, C.byref(sa), C.byref(sb), C.byref(o), bases, C.byref(ni)), "ivj_set_stats")
-        del keep_a, keep_b
+        del keep
         return int(bases[0]), int(bases[1]), int(bases[2]), int(ni.value)
 
     def multi_inter(self, frames, min_frames: int, mode: int, strict: bool, n_contigs: int):
@@ -912,25 +940,14 @@ class Engine:
         consensus), (contig id, start) order, bounds in the mode's own convention."""
         frames = list(frames)
         min_frames = check_multi(len(frames), min_frames, mode)
-        sides = (_Side * len(frames))()
-        keep = []
-        for f, frame in enumerate(frames):
-            side, arrays = _host_side(*frame)
-            sides[f] = side
-            keep.append(arrays)
+        sides, keep = _frames(frames)
         o = make_opts(strict, n_contigs)
         out = _Segments()
         _check(self.L, self.L.ivj_multi_inter(self.h, sides, len(frames), C.byref(o), min_frames, int(mode), C.byref(out)), "ivj_multi_inter")
         del keep
-        try:
-            n = out.n
-            with_mask = mode == MULTI_SEGMENTS
-            if n == 0:
-                return (*(np.empty(0, np.int32) for _ in range(3)), np.empty(0, np.uint64) if with_mask else None)
-            cols = tuple(np.ctypeslib.as_array(getattr(out, name), shape=(n,)).copy() for name in ("contig", "start", "end"))
-            return (*cols, np.ctypeslib.as_array(out.mask, shape=(n,)).copy() if with_mask else None)
-        finally:
-            self.L.ivj_segments_free(C.byref(out))
+        if mode == MULTI_SEGMENTS:
+            return _copy_columns(out, ("contig", "start", "end", "mask"), _I32x3 + (np.uint64,), self.L.ivj_segments_free)
+        return (*_copy_columns(out, ("contig", "start", "end"), _I32x3, self.L.ivj_segments_free), None)
 
     def multi_pairwise(self, frames, strict: bool, n_contigs: int):
         """pb.pairwise_jaccard over a list of (contig, start, end) frames: -> (bases, runs), two (F, F) int64 arrays, symmetric;
@@ -938,12 +955,7 @@ class Engine:
         their intersection (set_stats' n_intersections), from one walk over all frames."""
         frames = list(frames)
         check_multi(len(frames), 1)
-        sides = (_Side * len(frames))()
-        keep = []
-        for f, frame in enumerate(frames):
-            side, arrays = _host_side(*frame)
-            sides[f] = side
-            keep.append(arrays)
+        sides, keep = _frames(frames)
         o = make_opts(strict, n_contigs)
         bases = np.zeros((len(frames), len(frames)), np.int64)
         runs = np.zeros((len(frames), len(frames)), np.int64)
@@ -966,50 +978,42 @@ class Engine:
 
     def coverage(self, probe, build, strict: bool, n_contigs: int, partition_mode: int = 0) -> np.ndarray:
         """pb.coverage: covered positions of every probe row (int64, probe order)."""
-        ps, keep_p = _host_side(*probe)
-        bs, keep_b = _host_side(*build)
+        ps, bs, keep = _host_sides(probe, build)
         o = make_opts(strict, n_contigs, partition_mode=partition_mode)
         cov = np.empty(ps.n, np.int64)
         _check(self.L, self.L.ivj_coverage(self.h, C.byref(ps), C.byref(bs), C.byref(o), cov.ctypes.data), "ivj_coverage")
-        del keep_p, keep_b
+        del keep
         return cov
 
     def overlap_bases(self, probe, build, strict: bool, n_contigs: int, partition_mode: int = 0) -> np.ndarray:
         """pb.mean_depth: for every probe row the positions shared with each build row of its contig, summed (int64, probe order)."""
-        ps, keep_p = _host_side(*probe)
-        bs, keep_b = _host_side(*build)
+        ps, bs, keep = _host_sides(probe, build)
         o = make_opts(strict, n_contigs, partition_mode=partition_mode)
         bases = np.empty(ps.n, np.int64)
         _check(self.L, self.L.ivj_overlap_bases(self.h, C.byref(ps), C.byref(bs), C.byref(o), bases.ctypes.data), "ivj_overlap_bases")
-        del keep_p, keep_b
+        del keep
         return bases
 
     def depth_profile(self, windows, reverse, n_bins: int, build, strict: bool, n_contigs: int) -> np.ndarray:
         """pb.depth_profile: every window row cut into n_bins bins (edges S + floor(j L / n_bins)), per bin the positions shared with
         each build row of the window's contig, summed -> int64 (n, n_bins), window order.  ``reverse``: None or one flag per window;
         a flagged row comes back right to left."""
-        ws, keep_w = _host_side(*windows)
-        bs, keep_b = _host_side(*build)
+        ws, bs, keep = _host_sides(windows, build)
         o = make_opts(strict, n_contigs)
-        rev = None
-        if reverse is not None:
-            rev = np.ascontiguousarray(np.asarray(reverse).astype(bool).astype(np.uint8))
-            if rev.shape != (ws.n,):
-                raise ValueError(f"reverse must hold one flag per window ({ws.n}), got shape {rev.shape}")
+        rev = _reverse_flags(reverse, ws.n)
         n_bins = int(n_bins)
         # a bin count the entry refuses gets no matrix: the entry checks n_bins before it looks at the output
         bases = np.empty((ws.n, n_bins if 1 <= n_bins <= DEPTH_PROFILE_MAX_BINS else 0), np.int64)
         _check(self.L, self.L.ivj_depth_profile(self.h, C.byref(ws), rev.ctypes.data if rev is not None and ws.n else None, int(n_bins),
                                                  C.byref(bs), C.byref(o), bases.ctypes.data if bases.size else None), "ivj_depth_profile")
-        del keep_w, keep_b
+        del keep
         return bases
 
     def depth_summary(self, probe, build, strict: bool, n_contigs: int, thresholds=(1,), partition_mode: int = 0, want_max: bool = True):
         """pb.depth_summary: -> (max_depth int32[n], bases_ge int64[K, n]): per probe row the largest number of build rows of its
         contig that cover one of its positions, and per threshold T = thresholds[k] the number of its positions covered by at
         least T build rows (row k of bases_ge, the caller's order).  want_max=False: thresholds only, max_depth comes back None."""
-        ps, keep_p = _host_side(*probe)
-        bs, keep_b = _host_side(*build)
+        ps, bs, keep = _host_sides(probe, build)
         o = make_opts(strict, n_contigs, partition_mode=partition_mode)
         thr = np.ascontiguousarray(np.asarray(list(thresholds), dtype=np.int64).astype(np.int32))
         k = int(thr.shape[0])
@@ -1017,23 +1021,22 @@ class Engine:
         bg = np.empty((k, ps.n), np.int64)
         _check(self.L, self.L.ivj_depth_summary(self.h, C.byref(ps), C.byref(bs), C.byref(o), thr.ctypes.data if k else None, k,
                                                  md.ctypes.data if want_max else None, bg.ctypes.data if k else None), "ivj_depth_summary")
-        del keep_p, keep_b
+        del keep
         return md, bg
 
     def depth_hist(self, probe, build, strict: bool, n_contigs: int, max_depth: int, partition_mode: int = 0) -> np.ndarray:
         """pb.depth_histogram: -> int64 (n, max_depth + 1), probe order: bin d of a row = its positions that exactly d build rows of
         its contig cover, the last bin = max_depth or more; a row sums to its positions, bin 0 holds the uncovered ones."""
-        ps, keep_p = _host_side(*probe)
-        bs, keep_b = _host_side(*build)
+        ps, bs, keep = _host_sides(probe, build)
         o = make_opts(strict, n_contigs, partition_mode=partition_mode)
         max_depth = int(max_depth)
         # a depth the entry refuses gets no matrix: the entry checks max_depth before it looks at the output
         ok = 1 <= max_depth <= MAX_HIST_DEPTH
         hist = np.empty((ps.n, max_depth + 1 if ok else 0), np.int64)
-        keep = hist if hist.size else np.empty(1, np.int64)          # (an array without elements still has to pass a non-NULL address)
-        _check(self.L, self.L.ivj_depth_hist(self.h, C.byref(ps), C.byref(bs), C.byref(o), max_depth, keep.ctypes.data if ok else None),
+        keep_h = hist if hist.size else np.empty(1, np.int64)        # (an array without elements still has to pass a non-NULL address)
+        _check(self.L, self.L.ivj_depth_hist(self.h, C.byref(ps), C.byref(bs), C.byref(o), max_depth, keep_h.ctypes.data if ok else None),
                "ivj_depth_hist")
-        del keep_p, keep_b
+        del keep
         return hist
 
     def depth_hist_contigs(self, frame, strict: bool, n_contigs: int, max_depth: int) -> np.ndarray:
@@ -1054,8 +1057,7 @@ class Engine:
         """pb.depth_quantiles: ranks int64 (n, K), 0-based, K in 1 .. MAX_QUANT_RANKS -> int32 (n, K), probe order: cell (i, j) =
         the ranks[i, j]-th smallest depth of the build side over the positions of probe row i (uncovered positions count at
         depth 0); -1 for a rank outside [0, positions of the row) and for a row without a position or outside the dictionary."""
-        ps, keep_p = _host_side(*probe)
-        bs, keep_b = _host_side(*build)
+        ps, bs, keep = _host_sides(probe, build)
         o = make_opts(strict, n_contigs, partition_mode=partition_mode)
         ranks = np.ascontiguousarray(ranks, dtype=np.int64)
         if ranks.ndim != 2 or ranks.shape[0] != ps.n:
@@ -1067,23 +1069,16 @@ class Engine:
         keep_o = out if out.size else np.empty(1, np.int32)
         _check(self.L, self.L.ivj_depth_quantiles(self.h, C.byref(ps), C.byref(bs), C.byref(o), k, keep_r.ctypes.data, keep_o.ctypes.data),
                "ivj_depth_quantiles")
-        del keep_p, keep_b
+        del keep
         return out
 
     def _pieces(self, fn, name, a, b, strict, n_contigs, partition_mode=0):
-        sa, keep_a = _host_side(*a)
-        sb, keep_b = _host_side(*b)
+        sa, sb, keep = _host_sides(a, b)
         o = make_opts(strict, n_contigs, partition_mode=partition_mode)
         out = _Pieces()
         _check(self.L, fn(self.h, C.byref(sa), C.byref(sb), C.byref(o), C.byref(out)), name)
-        del keep_a, keep_b
-        try:
-            n = out.n
-            if n == 0:
-                return np.empty(0, np.int32), np.empty(0, np.int32), np.empty(0, np.int32)
-            return tuple(np.ctypeslib.as_array(getattr(out, k), shape=(n,)).copy() for k in ("row", "start", "end"))
-        finally:
-            self.L.ivj_pieces_free(C.byref(out))
+        del keep
+        return _copy_columns(out, ("row", "start", "end"), _I32x3, self.L.ivj_pieces_free)
 
     def subtract(self, left, right, strict: bool, n_contigs: int, partition_mode: int = 0):
         """pb.subtract: every left interval minus the union of the right ones -> (left row, start, end) pieces.
@@ -1095,13 +1090,12 @@ class Engine:
         return self._pieces(self.L.ivj_complement, "ivj_complement", frame, view, strict, n_contigs, partition_mode)
 
     def count_overlaps(self, probe, build, strict: bool, n_contigs: int, table_mode: int = 0, partition_mode: int = 0) -> np.ndarray:
-        ps, keep_p = _host_side(*probe)
-        bs, keep_b = _host_side(*build)
+        ps, bs, keep = _host_sides(probe, build)
         o = make_opts(strict, n_contigs, table_mode=table_mode, partition_mode=partition_mode)
         counts = np.empty(ps.n, np.int64)
         _check(self.L, self.L.ivj_count_overlaps(self.h, C.byref(ps), C.byref(bs), C.byref(o), counts.ctypes.data),
                "ivj_count_overlaps")
-        del keep_p, keep_b
+        del keep
         return counts
 
     def _host_thresholds(self, ps, bs, min_overlap, probe_min, build_min):
@@ -1113,31 +1107,24 @@ class Engine:
                        partition_mode: int = 0):
         """pb.overlap with overlap thresholds (ivj_overlap_thresh): the pairs with ov >= max(1, min_overlap, probe_min[probe row],
         build_min[build row]); the minima are uint32 base counts per row (0 none, THRESH_NEVER never) -> (probe_idx, build_idx)."""
-        ps, keep_p = _host_side(*probe)
-        bs, keep_b = _host_side(*build)
+        ps, bs, keep = _host_sides(probe, build)
         t, keep_t = self._host_thresholds(ps, bs, min_overlap, probe_min, build_min)
         o = make_opts(strict, n_contigs, partition_mode=partition_mode)
         out = _Pairs()
         _check(self.L, self.L.ivj_overlap_thresh(self.h, C.byref(ps), C.byref(bs), C.byref(o), C.byref(t), C.byref(out)), "ivj_overlap_thresh")
-        del keep_p, keep_b, keep_t
-        n = out.n_pairs
-        if n == 0:
-            self.L.ivj_pairs_free(C.byref(out))
-            return np.empty(0, np.int32), np.empty(0, np.int32)
-        owner = _PairsOwner(load_library(), out)
-        return _owned_view(out.probe_idx, n, owner), _owned_view(out.build_idx, n, owner)
+        del keep, keep_t
+        return self._pairs_result(out)
 
     def count_overlaps_thresh(self, probe, build, strict: bool, n_contigs: int, min_overlap: int = 0, probe_min=None, build_min=None,
                               partition_mode: int = 0) -> np.ndarray:
         """pb.count_overlaps with overlap thresholds (ivj_count_overlaps_thresh): int64 per probe row, probe order kept."""
-        ps, keep_p = _host_side(*probe)
-        bs, keep_b = _host_side(*build)
+        ps, bs, keep = _host_sides(probe, build)
         t, keep_t = self._host_thresholds(ps, bs, min_overlap, probe_min, build_min)
         o = make_opts(strict, n_contigs, partition_mode=partition_mode)
         counts = np.zeros(ps.n, np.int64)
         _check(self.L, self.L.ivj_count_overlaps_thresh(self.h, C.byref(ps), C.byref(bs), C.byref(o), C.byref(t), counts.ctypes.data),
                "ivj_count_overlaps_thresh")
-        del keep_p, keep_b, keep_t
+        del keep, keep_t
         return counts
 
     def _host_window(self, ps, left, right, probe_left, probe_right, min_distance):
@@ -1151,45 +1138,40 @@ class Engine:
         row's entry of the uint32 columns ``probe_left`` / ``probe_right``) and at least ``min_distance`` away; the semantics are
         those of include/ivjoin.h -> (probe_idx, build_idx, dist): dist the signed int64 distances (negative: the build row lies
         before the probe row), or None with ``distance=False``."""
-        ps, keep_p = _host_side(*probe)
-        bs, keep_b = _host_side(*build)
+        ps, bs, keep = _host_sides(probe, build)
         w, keep_w = self._host_window(ps, left, right, probe_left, probe_right, min_distance)
         o = make_opts(strict, n_contigs, partition_mode=partition_mode)
         out = _Pairs()
         dist = C.POINTER(C.c_int64)()
         _check(self.L, self.L.ivj_overlap_window(self.h, C.byref(ps), C.byref(bs), C.byref(o), C.byref(w), C.byref(out),
                                                  C.byref(dist) if distance else None), "ivj_overlap_window")
-        del keep_p, keep_b, keep_w
+        del keep, keep_w
         n = out.n_pairs
-        if n == 0:
-            self.L.ivj_pairs_free(C.byref(out))
-            return np.empty(0, np.int32), np.empty(0, np.int32), (np.empty(0, np.int64) if distance else None)
-        owner = _PairsOwner(load_library(), out)
         d = None
-        if distance:
+        if distance and n == 0:
+            d = np.empty(0, np.int64)
+        elif distance:
             buf = (C.c_int64 * n).from_address(C.addressof(dist.contents))
             buf._owner = _DistOwner(load_library(), dist)
             d = np.frombuffer(buf, dtype=np.int64)
-        return _owned_view(out.probe_idx, n, owner), _owned_view(out.build_idx, n, owner), d
+        return (*self._pairs_result(out), d)
 
     def count_window(self, probe, build, strict: bool, n_contigs: int, left: int = 0, right: int = 0, min_distance: int = 0,
                      probe_left=None, probe_right=None, partition_mode: int = 0) -> np.ndarray:
         """pb.count_window (ivj_count_window): the number of pairs ``overlap_window`` reports per probe row, int64, probe order kept."""
-        ps, keep_p = _host_side(*probe)
-        bs, keep_b = _host_side(*build)
+        ps, bs, keep = _host_sides(probe, build)
         w, keep_w = self._host_window(ps, left, right, probe_left, probe_right, min_distance)
         o = make_opts(strict, n_contigs, partition_mode=partition_mode)
         counts = np.zeros(ps.n, np.int64)
         _check(self.L, self.L.ivj_count_window(self.h, C.byref(ps), C.byref(bs), C.byref(o), C.byref(w), counts.ctypes.data), "ivj_count_window")
-        del keep_p, keep_b, keep_w
+        del keep, keep_w
         return counts
 
     def permute_overlaps(self, probe, build, strict: bool, n_contigs: int, contig_len, offsets, partition_mode: int = 0):
         """pb.permutation_test (ivj_permute_overlaps): ``contig_len`` int32[n_contigs] (>= 1), ``offsets`` int32[n_perm, n_contigs]
         with 0 <= offsets[p, c] < contig_len[c].  -> (n_pairs int64[n_perm], n_rows int64[n_perm]): per permutation the matches
         summed over the circularly shifted probe rows and their pieces, and the probe rows with a match (include/ivjoin.h)."""
-        ps, keep_p = _host_side(*probe)
-        bs, keep_b = _host_side(*build)
+        ps, bs, keep = _host_sides(probe, build)
         o = make_opts(strict, n_contigs, partition_mode=partition_mode)
         lens = np.ascontiguousarray(contig_len, dtype=np.int32).reshape(-1)
         off = np.ascontiguousarray(offsets, dtype=np.int32)
@@ -1200,7 +1182,7 @@ class Engine:
         _check(self.L, self.L.ivj_permute_overlaps(self.h, C.byref(ps), C.byref(bs), C.byref(o), lens.ctypes.data if n_contigs else None,
                                                    off.ctypes.data if off.size else None, n_perm, pairs.ctypes.data, rows.ctypes.data),
                "ivj_permute_overlaps")
-        del keep_p, keep_b
+        del keep
         return pairs, rows
 
     def _optional_thresholds(self, ps, bs, min_overlap, probe_min, build_min):
@@ -1219,12 +1201,10 @@ class Engine:
         keep, results = [], []
         size = int(np.prod(shape))
         for k, (values, valid, ops) in enumerate(agg):
-            values, valid, ops = _agg_column(values, valid, ops, n_build)
-            keep.append((values, valid))
-            cols[k] = _AggIn(values.ctypes.data if n_build else None, valid.ctypes.data if valid is not None and n_build else None,
-                             AGG_I64 if values.dtype == np.int64 else AGG_F64, ops)
+            cols[k], values, arrays = _agg_in(values, valid, ops, n_build)
+            keep.append(arrays)
             kinds = {"sum": values.dtype, "min": values.dtype, "max": values.dtype, "mean": np.float64, "count": np.int64}
-            res = {name: np.zeros(shape, kinds[name]) for name, bit in AGG_OPS.items() if ops & bit}
+            res = {name: np.zeros(shape, kinds[name]) for name, bit in AGG_OPS.items() if cols[k].ops & bit}
             outs[k] = _AggOut(*(res[name].ctypes.data if name in res and size else None for name in ("sum", "min", "max", "mean", "count")))
             results.append(res)
         return len(agg), cols, outs, results, keep
@@ -1246,33 +1226,27 @@ class Engine:
         return self._overlap_agg_call("ivj_overlap_wagg", probe, build, strict, n_contigs, agg, min_overlap, probe_min, build_min, partition_mode)
 
     def _overlap_agg_call(self, entry, probe, build, strict, n_contigs, agg, min_overlap, probe_min, build_min, partition_mode):
-        ps, keep_p = _host_side(*probe)
-        bs, keep_b = _host_side(*build)
+        ps, bs, keep = _host_sides(probe, build)
         t, keep_t = self._optional_thresholds(ps, bs, min_overlap, probe_min, build_min)
         o = make_opts(strict, n_contigs, partition_mode=partition_mode)
-        k, cols, outs, results, keep = self._agg_columns(agg, bs.n, (ps.n,))
+        k, cols, outs, results, keep_a = self._agg_columns(agg, bs.n, (ps.n,))
         _check(self.L, getattr(self.L, entry)(self.h, C.byref(ps), C.byref(bs), C.byref(o), t, k, cols, outs), entry)
-        del keep_p, keep_b, keep_t, keep
+        del keep, keep_t, keep_a
         return results
 
     def signal_profile(self, windows, reverse, n_bins: int, build, strict: bool, n_contigs: int, agg):
         """pb.signal_profile (ivj_signal_profile): every window row cut into n_bins bins as by ``depth_profile``, every bin a probe of
         ``overlap_wagg`` without thresholds -> [dict per column] of (n, n_bins) arrays, window order; ``reverse``: None or one flag
         per window, a flagged row comes back right to left."""
-        ws, keep_w = _host_side(*windows)
-        bs, keep_b = _host_side(*build)
+        ws, bs, keep = _host_sides(windows, build)
         o = make_opts(strict, n_contigs)
-        rev = None
-        if reverse is not None:
-            rev = np.ascontiguousarray(np.asarray(reverse).astype(bool).astype(np.uint8))
-            if rev.shape != (ws.n,):
-                raise ValueError(f"reverse must hold one flag per window ({ws.n}), got shape {rev.shape}")
+        rev = _reverse_flags(reverse, ws.n)
         n_bins = int(n_bins)
         # a bin count the entry refuses gets no matrix: the entry checks n_bins before it looks at the outputs
-        k, cols, outs, results, keep = self._agg_columns(agg, bs.n, (ws.n, n_bins if 1 <= n_bins <= DEPTH_PROFILE_MAX_BINS else 0))
+        k, cols, outs, results, keep_a = self._agg_columns(agg, bs.n, (ws.n, n_bins if 1 <= n_bins <= DEPTH_PROFILE_MAX_BINS else 0))
         _check(self.L, self.L.ivj_signal_profile(self.h, C.byref(ws), rev.ctypes.data if rev is not None and ws.n else None, n_bins,
                                                   C.byref(bs), C.byref(o), k, cols, outs), "ivj_signal_profile")
-        del keep_w, keep_b, keep
+        del keep, keep_a
         return results
 
     def overlap_select(self, probe, build, strict: bool, n_contigs: int, mode, min_overlap: int = 0, probe_min=None, build_min=None,
@@ -1281,43 +1255,32 @@ class Engine:
         SELECT_ANTI) build row under the predicate -- the plain one, or the thresholded one when min_overlap / probe_min / build_min
         are given -- as an ascending int32 array.  The counts stay on the device; no pair is enumerated."""
         mode = select_mode(mode)
-        ps, keep_p = _host_side(*probe)
-        bs, keep_b = _host_side(*build)
+        ps, bs, keep = _host_sides(probe, build)
         t, keep_t = self._optional_thresholds(ps, bs, min_overlap, probe_min, build_min)
         o = make_opts(strict, n_contigs, partition_mode=partition_mode)
         out = _RowSel()
         _check(self.L, self.L.ivj_overlap_select(self.h, C.byref(ps), C.byref(bs), C.byref(o), t, mode, C.byref(out)), "ivj_overlap_select")
-        del keep_p, keep_b, keep_t
-        try:
-            return np.ctypeslib.as_array(out.rows, shape=(out.n,)).copy() if out.n else np.empty(0, np.int32)
-        finally:
-            self.L.ivj_rowsel_free(C.byref(out))
+        del keep, keep_t
+        return _copy_columns(out, ("rows",), (np.int32,), self.L.ivj_rowsel_free)[0]
 
     def overlap_outer(self, probe, build, strict: bool, n_contigs: int, min_overlap: int = 0, probe_min=None, build_min=None,
                       partition_mode: int = 0):
         """Left outer join (ivj_overlap_outer): the inner pairs as ``overlap`` (``overlap_thresh`` with thresholds) returns them,
         then (row, -1) for every probe row without a match, ascending -> (probe_idx, build_idx)."""
-        ps, keep_p = _host_side(*probe)
-        bs, keep_b = _host_side(*build)
+        ps, bs, keep = _host_sides(probe, build)
         t, keep_t = self._optional_thresholds(ps, bs, min_overlap, probe_min, build_min)
         o = make_opts(strict, n_contigs, partition_mode=partition_mode)
         out = _Pairs()
         _check(self.L, self.L.ivj_overlap_outer(self.h, C.byref(ps), C.byref(bs), C.byref(o), t, C.byref(out)), "ivj_overlap_outer")
-        del keep_p, keep_b, keep_t
-        n = out.n_pairs
-        if n == 0:
-            self.L.ivj_pairs_free(C.byref(out))
-            return np.empty(0, np.int32), np.empty(0, np.int32)
-        owner = _PairsOwner(load_library(), out)
-        return _owned_view(out.probe_idx, n, owner), _owned_view(out.build_idx, n, owner)
+        del keep, keep_t
+        return self._pairs_result(out)
 
     def nearest(self, probe, build, strict: bool, n_contigs: int, k: int = 1, include_overlaps: bool = True,
                 table_mode: int = 0, partition_mode: int = 0, nearest_ignore: int = 0):
         """partition_mode 0 auto / 1 bucket the probe side first / 2 never: same result, probe order kept.
         nearest_ignore: NEAREST_IGNORE_LEFT (1) leaves out the rows before the probe, NEAREST_IGNORE_RIGHT (2) the rows after it
         (overlapping rows always count); the rest of the ordered candidate list, cut to k."""
-        ps, keep_p = _host_side(*probe)
-        bs, keep_b = _host_side(*build)
+        ps, bs, keep = _host_sides(probe, build)
         if k < 1:
             raise ValueError("k must be >= 1")
         o = make_opts(strict, n_contigs, k, include_overlaps, table_mode=table_mode, partition_mode=partition_mode, nearest_ignore=nearest_ignore)
@@ -1326,7 +1289,7 @@ class Engine:
         nf = np.empty(ps.n, np.int32)
         _check(self.L, self.L.ivj_nearest(self.h, C.byref(ps), C.byref(bs), C.byref(o), idx.ctypes.data,
                                            dist.ctypes.data, nf.ctypes.data), "ivj_nearest")
-        del keep_p, keep_b
+        del keep
         return idx, dist, nf
 
     # ---- device-resident entry points (raw device pointers) -----------------
