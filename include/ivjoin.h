@@ -591,6 +591,45 @@ int ivj_overlap_agg_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, 
                         const ivj_thresholds* thr_dev /* NULL = plain predicate */, int64_t n_values, int32_t n_cols,
                         const ivj_agg_in* cols, const ivj_agg_out* agg_out);
 
+/* ---- map_quantiles: exact quantiles of a build-side value column over each probe row's overlaps (bedtools map -o median) -------------
+ * For a probe (df1) row a take the build (df2) rows that match a -- "match" as ivj_overlap_agg defines it for the same call: the
+ * plain predicate with thr == NULL, the thresholded one with an ivj_thresholds -- and whose value is valid (a row outside
+ * [0, n_values) is invalid; a probe outside the dictionary matches nothing).  Let m be their number and v[0] <= ... <= v[m - 1]
+ * their values in ascending order: int64 columns in signed order, double columns in the order of a numeric sort with NaN last,
+ * -inf < ... < -0.0 = +0.0 < ... < +inf < NaN; every NaN is one value and comes back as the canonical quiet NaN; which zero is
+ * returned where both signs tie at a rank is unspecified.  For each of the n_q requests (q[j] in [0, 1], upper[j] in {0, 1};
+ * upper == NULL: all 0), shared by all rows:
+ *     h = q[j] * (double)(m - 1)   (one IEEE round-to-nearest product),   rank = upper[j] ? ceil(h) : floor(h),
+ *     out[a * n_q + j] = v[rank],   count[a] = m;
+ * where m == 0, out[a * n_q + *] is written as all-zero bits and count[a] = 0.  col is ONE build column (ivj_agg_in; ops is
+ * ignored); out holds the column's 8-byte type.  Results are in probe order whatever opts->partition_mode; a probe row_id is
+ * ignored.  No pair is enumerated, nothing is sorted and there is no global atomic: results are identical from run to run.
+ * The kernel (csrc/overlap_quant.hip.h) is a radix select over the candidates of each row, IVJ_OVQ_BITS bits per pass, with a
+ * 2^IVJ_OVQ_BITS-bin 32-bit histogram per (row, request) in LDS; a workgroup owns
+ * P = floor(IVJ_OVQ_LDS_BYTES / (n_q * 2^IVJ_OVQ_BITS * 4)) consecutive probe rows, clamped to [1, IVJ_OVQ_MAX_TILE] (informative:
+ * the result does not depend on them; IVJ_OVQ_BITS may be set when the library is compiled, 4 .. 8).
+ * Cost: per CANDIDATE of the probe's loose range (not per match) one 16-byte record and the predicate, per match 8 value bytes
+ * and up to n_q LDS reads and adds -- paid 1 + npass times, npass = the number of IVJ_OVQ_BITS-bit digits in which the keys under
+ * a workgroup's rows differ (at most ceil(64 / IVJ_OVQ_BITS); few for small integers and for float32 values of one sign widened to double).
+ * IVJ_EINVAL: n_q outside [1, IVJ_MAX_OVQ_RANKS], a q outside [0, 1] or NaN, an unknown dtype, NULL values with build rows
+ * present, a NULL out with probe rows present, a non-NULL thr with nothing set.  IVJ_ESTATE: an index without lookup tables
+ * (with_end_order & 2).  (New entries change no existing struct or signature: IVJ_ABI_VERSION stays.) */
+#define IVJ_MAX_OVQ_RANKS 16
+#ifndef IVJ_OVQ_BITS
+#define IVJ_OVQ_BITS 4
+#endif
+#define IVJ_OVQ_LDS_BYTES 49152
+#define IVJ_OVQ_MAX_TILE 512
+/* Host form: out (probe->n x n_q, row-major) and count (probe->n entries; may be NULL) are CALLER-owned host buffers. */
+int ivj_overlap_quantiles(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts,
+                          const ivj_thresholds* thr /* NULL = plain predicate */, const ivj_agg_in* col /* ONE build column, ops ignored */,
+                          int32_t n_q, const double* q, const uint8_t* upper, void* out, int64_t* count);
+/* Device form on an index of ivj_index_build_dev: values / valid / out / count are device pointers, n_values = rows behind
+ * col->values; q and upper are HOST arrays of n_q entries; enqueued on the context's stream. */
+int ivj_overlap_quantiles_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, const ivj_opts* opts,
+                              const ivj_thresholds* thr_dev /* NULL = plain predicate */, int64_t n_values, const ivj_agg_in* col,
+                              int32_t n_q, const double* q /* HOST */, const uint8_t* upper /* HOST */, void* out_dev, int64_t* count_dev);
+
 /* ---- signal_summary / signal_profile: build-side values weighted by the positions they share with the probe ------------------------
  * The build (df2) side read as a signal track, (contig, start, end, value) rows as in a bedGraph: what bigWigAverageOverBed and
  * deepTools computeMatrix compute.  For a probe row a and a build row b of one contig

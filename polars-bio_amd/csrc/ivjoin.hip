@@ -44,6 +44,7 @@
 #include "select.hip.h"
 #include "merge_agg.hip.h"
 #include "overlap_agg.hip.h"
+#include "overlap_quant.hip.h"
 #include "signal.hip.h"
 #include "permute.hip.h"
 
@@ -70,6 +71,7 @@ using namespace ivj;
 #include "host_window.hip.h"
 #include "host_select.hip.h"
 #include "host_overlap_agg.hip.h"
+#include "host_overlap_quant.hip.h"
 #include "host_signal.hip.h"
 #include "host_permute.hip.h"
 #include "host_stream.hip.h"
@@ -1535,6 +1537,53 @@ int ivj_overlap_agg(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, 
     IVJ_TRY(overlap_agg_plan(ctx, ix, &U.H.dp.s, opts, U.dthr, P));
     return agg_cols_host(ctx, n, nb, n_cols, cols, agg_out,
                          [&](const ivj_agg_in& in, const ivj_agg_out& dev) { return overlap_agg_col(ctx, ix, P, in, nb, dev); });
+} IVJ_ABI_CATCH
+
+// ---------------------------------------------------------------- map_quantiles: order statistics of build values per probe row (overlap_quant.hip.h)
+
+int ivj_overlap_quantiles_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe_dev, const ivj_opts* opts, const ivj_thresholds* thr_dev,
+                              int64_t n_values, const ivj_agg_in* col, int32_t n_q, const double* q, const uint8_t* upper, void* out_dev,
+                              int64_t* count_dev) try {
+    if (!ctx || !ix) return fail(IVJ_EINVAL, "ctx or index is NULL");
+    if (n_values < 0) return fail(IVJ_EINVAL, "n_values < 0");
+    IVJ_TRY(overlap_quant_check(opts, probe_dev, thr_dev, col, n_q, q, out_dev, ix->n > 0 && n_values > 0));
+    DeviceGuard g(ctx->device);
+    OaggPlan P;
+    IVJ_TRY(overlap_agg_plan(ctx, ix, probe_dev, opts, thr_dev, P));
+    return overlap_quant_col(ctx, ix, P, *col, n_values, n_q, q, upper, out_dev, count_dev);
+} IVJ_ABI_CATCH
+
+int ivj_overlap_quantiles(ivj_ctx* ctx, const ivj_side* probe, const ivj_side* build, const ivj_opts* opts, const ivj_thresholds* thr,
+                          const ivj_agg_in* col, int32_t n_q, const double* q, const uint8_t* upper, void* out, int64_t* count) try {
+    if (!ctx) return fail(IVJ_EINVAL, "ctx is NULL");
+    IVJ_TRY(check_side(build, "build"));
+    IVJ_TRY(overlap_quant_check(opts, probe, thr, col, n_q, q, out, build->n > 0));
+    const int64_t n = probe->n, nb = build->n;
+    if (n == 0) return IVJ_OK;
+    DeviceGuard g(ctx->device);
+    SelectHost U;
+    IVJ_TRY(select_upload(ctx, probe, build, opts, thr, U));
+    ivj_index* ix = U.H.h.ix;
+    OaggPlan P;
+    IVJ_TRY(overlap_agg_plan(ctx, ix, &U.H.dp.s, opts, U.dthr, P));
+    // one block: the value column and its validity bytes, then the answers and the counts
+    const size_t val8 = align_up((size_t)(nb + 1) * 8), val1 = align_up((size_t)nb + 1), out8 = align_up((size_t)n * (size_t)n_q * 8);
+    DevBuf stage;
+    IVJ_TRY(devbuf_alloc(stage, val8 + val1 + out8 + align_up((size_t)n * 8), "value column and quantiles"));
+    char* base = (char*)stage.p;
+    uint8_t* d_valid = (uint8_t*)(base + val8);
+    void* d_out = base + val8 + val1;
+    int64_t* d_count = (int64_t*)(base + val8 + val1 + out8);
+    const bool with_valid = nb > 0 && col->valid;
+    {
+        HostXfer copy(ctx->stream, &ctx->xfer);
+        if (nb > 0) copy.h2d(base, col->values, (size_t)nb * 8);
+        if (with_valid) copy.h2d(d_valid, col->valid, (size_t)nb);
+        HIP_TRY(copy.finish());
+    }
+    const ivj_agg_in in{base, with_valid ? d_valid : nullptr, col->dtype, col->ops};
+    IVJ_TRY(overlap_quant_col(ctx, ix, P, in, nb, n_q, q, upper, d_out, d_count));
+    return d2h_finish(ctx, {{out, d_out, (size_t)n * (size_t)n_q * 8}, {count, d_count, count ? (size_t)n * 8 : 0}});
 } IVJ_ABI_CATCH
 
 // ---------------------------------------------------------------- signal_summary / signal_profile: overlap-weighted build values (signal.hip.h)

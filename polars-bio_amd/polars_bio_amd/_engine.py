@@ -36,7 +36,7 @@ ABI_SYMBOLS = [
     "ivj_subtract", "ivj_complement", "ivj_pieces_free", "ivj_subtract_dev",
     "ivj_merge", "ivj_merged_free", "ivj_cluster", "ivj_coverage", "ivj_cluster_dev", "ivj_merge_dev", "ivj_coverage_dev",
     "ivj_merge_agg", "ivj_merge_agg_free", "ivj_merge_agg_dev",
-    "ivj_overlap_agg", "ivj_overlap_agg_dev", "ivj_permute_overlaps", "ivj_permute_overlaps_dev",
+    "ivj_overlap_agg", "ivj_overlap_agg_dev", "ivj_overlap_quantiles", "ivj_overlap_quantiles_dev", "ivj_permute_overlaps", "ivj_permute_overlaps_dev",
     "ivj_overlap_wagg", "ivj_overlap_wagg_dev", "ivj_signal_profile", "ivj_signal_profile_dev",
     "ivj_overlap_bases", "ivj_overlap_bases_dev", "ivj_depth_profile", "ivj_depth_profile_dev",
     "ivj_depth", "ivj_blocks_free", "ivj_depth_dev", "ivj_depth_summary", "ivj_depth_summary_dev",
@@ -77,6 +77,15 @@ QUANT_BITS, QUANT_LDS_BYTES, QUANT_MAX_TILE = 4, 65536, 512      # include/ivjoi
 def depth_quant_tile(n_ranks: int) -> int:
     """probe rows one workgroup of ivj_depth_quantiles owns (include/ivjoin.h); informative: the result does not depend on it"""
     return min(max(QUANT_LDS_BYTES // (int(n_ranks) * (1 << QUANT_BITS) * 8), 1), QUANT_MAX_TILE)
+
+MAX_OVQ_RANKS = 16                   # include/ivjoin.h: IVJ_MAX_OVQ_RANKS, ivj_overlap_quantiles accepts 1 .. this many requests per call
+OVQ_BITS, OVQ_LDS_BYTES, OVQ_MAX_TILE = 4, 49152, 512            # include/ivjoin.h: IVJ_OVQ_BITS, IVJ_OVQ_LDS_BYTES, IVJ_OVQ_MAX_TILE
+
+
+def overlap_quant_tile(n_q: int) -> int:
+    """probe rows one workgroup of ivj_overlap_quantiles owns (include/ivjoin.h); informative: the result does not depend on it"""
+    return min(max(OVQ_LDS_BYTES // (int(n_q) * (1 << OVQ_BITS) * 4), 1), OVQ_MAX_TILE)
+
 
 # the operations of ivj_setop / ivj_setop_dev (include/ivjoin.h: IVJ_SETOP_*)
 SETOP_INTERSECTION, SETOP_UNION, SETOP_DIFFERENCE, SETOP_SYMMETRIC_DIFFERENCE = 0, 1, 2, 3
@@ -304,6 +313,8 @@ def load_library() -> C.CDLL:
         L.ivj_overlap_agg.argtypes = [vp, P, P, O, T, C.c_int32, C.POINTER(_AggIn), C.POINTER(_AggOut)]
         L.ivj_overlap_agg_dev.argtypes = [vp, vp, P, O, T, C.c_int64, C.c_int32, C.POINTER(_AggIn), C.POINTER(_AggOut)]
         L.ivj_overlap_wagg.argtypes = L.ivj_overlap_agg.argtypes
+        L.ivj_overlap_quantiles.argtypes = [vp, P, P, O, T, C.POINTER(_AggIn), C.c_int32, vp, vp, vp, vp]
+        L.ivj_overlap_quantiles_dev.argtypes = [vp, vp, P, O, T, C.c_int64, C.POINTER(_AggIn), C.c_int32, vp, vp, vp, vp]
         L.ivj_overlap_wagg_dev.argtypes = L.ivj_overlap_agg_dev.argtypes
         L.ivj_signal_profile.argtypes = [vp, P, vp, C.c_int32, P, O, C.c_int32, C.POINTER(_AggIn), C.POINTER(_AggOut)]
         L.ivj_signal_profile_dev.argtypes = [vp, vp, P, vp, C.c_int32, O, C.c_int64, C.c_int32, C.POINTER(_AggIn), C.POINTER(_AggOut)]
@@ -636,6 +647,16 @@ def _agg_in(values, valid, ops, n: int):
     col = _AggIn(values.ctypes.data if n else None, valid.ctypes.data if valid is not None and n else None,
                  AGG_I64 if values.dtype == np.int64 else AGG_F64, ops)
     return col, values, (values, valid)
+
+
+def _quantile_requests(q, upper):
+    """The (q, upper) requests of ivj_overlap_quantiles as contiguous float64 / uint8 arrays of one length; the library
+    validates their number and values."""
+    qs = np.ascontiguousarray(np.atleast_1d(np.asarray(q, np.float64)).ravel())
+    up = np.ascontiguousarray(np.atleast_1d(np.asarray(upper)).astype(bool).astype(np.uint8).ravel())
+    if qs.shape != up.shape:
+        raise ValueError(f"q has {qs.size} entries, upper has {up.size}")
+    return qs, up
 
 
 def _copy_columns(out, names, dtypes, free=None):
@@ -1234,6 +1255,27 @@ class Engine:
         del keep, keep_t, keep_a
         return results
 
+    def overlap_quantiles(self, probe, build, strict: bool, n_contigs: int, values, valid, q, upper, min_overlap: int = 0, probe_min=None,
+                          build_min=None, partition_mode: int = 0):
+        """pb.map_quantiles (ivj_overlap_quantiles): ``values`` (int64 / float64) and ``valid`` (or None) = ONE value column of the
+        BUILD side; ``q`` = 1 .. MAX_OVQ_RANKS floats in [0, 1] and ``upper`` = one flag per q, shared by all rows.  Every probe row
+        sorts the valid values of the build rows it matches (predicate as ``overlap_agg``; int64 signed, doubles as np.sort with
+        NaN last) and answers v[floor(q (m - 1))], or v[ceil(q (m - 1))] where ``upper`` is set -> (out (n, n_q) in the values'
+        dtype, count int64 (n,) = m), probe order kept; a row with m == 0 holds zeros."""
+        ps, bs, keep = _host_sides(probe, build)
+        t, keep_t = self._optional_thresholds(ps, bs, min_overlap, probe_min, build_min)
+        o = make_opts(strict, n_contigs, partition_mode=partition_mode)
+        col, values, keep_a = _agg_in(values, valid, AGG_COUNT, bs.n)
+        qs, up = _quantile_requests(q, upper)
+        n_q = len(qs)
+        out = np.zeros((ps.n, n_q if 1 <= n_q <= MAX_OVQ_RANKS else 0), values.dtype)
+        count = np.zeros(ps.n, np.int64)
+        _check(self.L, self.L.ivj_overlap_quantiles(self.h, C.byref(ps), C.byref(bs), C.byref(o), t, C.byref(col), n_q, qs.ctypes.data,
+                                                    up.ctypes.data, out.ctypes.data if out.size else None,
+                                                    count.ctypes.data if ps.n else None), "ivj_overlap_quantiles")
+        del keep, keep_t, keep_a
+        return out, count
+
     def signal_profile(self, windows, reverse, n_bins: int, build, strict: bool, n_contigs: int, agg):
         """pb.signal_profile (ivj_signal_profile): every window row cut into n_bins bins as by ``depth_profile``, every bin a probe of
         ``overlap_wagg`` without thresholds -> [dict per column] of (n, n_bins) arrays, window order; ``reverse``: None or one flag
@@ -1490,6 +1532,18 @@ class Engine:
             cout[i] = _AggOut(*(outs[i].get(name) or None for name in ("sum", "min", "max", "mean", "count")))
         _check(self.L, self.L.ivj_overlap_agg_dev(self.h, ix.handle, C.byref(probe), C.byref(opts), C.byref(thr) if thr is not None else None,
                                                   int(n_values), k, cin, cout), "ivj_overlap_agg_dev")
+
+    def overlap_quantiles_dev(self, ix: DeviceIndex, probe: _Side, opts: _Opts, thr: Optional[_Thresholds], n_values: int, col, q, upper,
+                              out_ptr: int, count_ptr: int):
+        """ivj_overlap_quantiles_dev; ``thr`` None = the plain predicate.  ``col`` = (values_ptr, valid_ptr or 0, dtype AGG_I64 /
+        AGG_F64) of the build side's value column; ``q`` / ``upper`` are host sequences; ``out_ptr``: probe.n x len(q) elements of
+        the column's type, ``count_ptr``: probe.n int64 or 0."""
+        values_ptr, valid_ptr, dtype = col
+        cin = _AggIn(values_ptr or None, valid_ptr or None, int(dtype), 0)
+        qs, up = _quantile_requests(q, upper)
+        _check(self.L, self.L.ivj_overlap_quantiles_dev(self.h, ix.handle, C.byref(probe), C.byref(opts), C.byref(thr) if thr is not None else None,
+                                                        int(n_values), C.byref(cin), len(qs), qs.ctypes.data, up.ctypes.data,
+                                                        C.c_void_p(out_ptr or None), C.c_void_p(count_ptr or None)), "ivj_overlap_quantiles_dev")
 
     def overlap_wagg_dev(self, ix: DeviceIndex, probe: _Side, opts: _Opts, thr: Optional[_Thresholds], n_values: int, cols, outs):
         """ivj_overlap_wagg_dev; ``thr`` None = every row that shares a position.  Arguments as ``overlap_agg_dev``; the ``count``

@@ -393,6 +393,38 @@ class DeviceJoin:
                 ix.close()
         return results
 
+    # ---- map_quantiles (include/ivjoin.h: ivj_overlap_quantiles_dev) -----------------------------------
+    def overlap_quantiles(self, probe: DeviceSide, build: DeviceSide, strict: bool, n_contigs: int, values, valid, q, upper,
+                          min_overlap: int = 0, probe_min=None, build_min=None, index=None, partition_mode: int = 0):
+        """Exact order statistics of ONE build-side value column over each probe row's matches (ivj_overlap_quantiles_dev), all in
+        HBM.  ``values`` / ``valid`` as one column of ``overlap_agg``; ``q`` / ``upper``: host sequences of 1 .. 16 floats in
+        [0, 1] and one flag each.  With the m valid matched values of a row sorted (int64 signed; doubles as a numeric sort, NaN
+        last): cell (row, j) = v[floor(q_j (m - 1))], or v[ceil(q_j (m - 1))] where upper_j is set.  The predicate is the plain one,
+        or the thresholded one when min_overlap / probe_min / build_min are given.  -> (out (probe.n, len(q)) in the values'
+        dtype, count int64 (probe.n,) = m), probe order; rows with m == 0 hold zeros."""
+        torch = self.torch
+        opts = make_opts(strict, n_contigs, partition_mode=partition_mode)
+        plain = not min_overlap and probe_min is None and build_min is None
+        thr = None if plain else self._thresholds(probe, build, min_overlap, probe_min, build_min)
+        (values, valid, dtype, _), = self._agg_columns([(values, valid, "count")])[0]
+        n_values = int(values.shape[0])
+        n_q = len(q)
+        dev = probe.start.device
+        out = torch.zeros((probe.n, n_q), dtype=values.dtype, device=dev)
+        count = torch.zeros(probe.n, dtype=torch.int64, device=dev)
+        if build.n == 0:
+            plain, thr = True, None                            # every count is 0 under either predicate
+        own = index is None
+        ix = self.engine.index_build_dev(build.as_c(), opts, plain) if own else index
+        try:
+            self.engine.overlap_quantiles_dev(ix, probe.as_c(), opts, thr, n_values,
+                                              (values.data_ptr() if n_values else 0, valid.data_ptr() if valid is not None and n_values else 0, dtype),
+                                              q, upper, out.data_ptr() if out.numel() else 0, count.data_ptr() if probe.n else 0)
+        finally:
+            if own:
+                ix.close()
+        return out, count
+
     def signal_profile(self, windows: DeviceSide, build: DeviceSide, strict: bool, n_contigs: int, n_bins: int, agg, reverse=None,
                        index=None):
         """Every window row cut into ``n_bins`` bins as by ``depth_profile``, every bin a probe of ``overlap_wagg`` without

@@ -18,6 +18,7 @@ _ALIASES = {
     "depth_profile": (range_op.depth_profile, True), "depth_histogram": (range_op.depth_histogram, True),
     "depth_quantiles": (range_op.depth_quantiles, True), "median_depth": (range_op.median_depth, True),
     "subtract": (range_op.subtract, True), "map_overlaps": (range_op.map_overlaps, True),
+    "map_quantiles": (range_op.map_quantiles, True), "map_median": (range_op.map_median, True),
     "signal_summary": (range_op.signal_summary, True), "signal_profile": (range_op.signal_profile, True),
     "permutation_test": (range_op.permutation_test, True),
     "merge": (range_op.merge, False), "depth": (range_op.depth, False), "genome_depth_histogram": (range_op.genome_depth_histogram, False), "cluster": (range_op.cluster, False), "complement": (range_op.complement, False),

@@ -27,7 +27,7 @@ from .constants import DEFAULT_INTERVAL_COLUMNS
 
 logger = logging.getLogger("polars_bio_amd")
 
-__all__ = ["overlap", "window", "count_window", "window_extents", "overlap_batches", "count_overlaps_batches", "nearest_batches", "nearest", "count_overlaps", "coverage", "mean_depth", "depth_profile", "depth_summary", "depth_histogram", "genome_depth_histogram", "depth_quantiles", "median_depth", "quantile_ranks", "merge", "cluster", "complement", "subtract", "map_overlaps", "signal_summary", "signal_profile",
+__all__ = ["overlap", "window", "count_window", "window_extents", "overlap_batches", "count_overlaps_batches", "nearest_batches", "nearest", "count_overlaps", "coverage", "mean_depth", "depth_profile", "depth_summary", "depth_histogram", "genome_depth_histogram", "depth_quantiles", "median_depth", "quantile_ranks", "merge", "cluster", "complement", "subtract", "map_overlaps", "map_quantiles", "map_median", "signal_summary", "signal_profile",
            "set_intersect", "set_union", "set_difference", "set_symmetric_difference", "jaccard", "multi_intersect", "consensus", "pairwise_jaccard",
            "FilterOp", "RangeOp", "OverlapOutputMode"]
 
@@ -1646,8 +1646,8 @@ def map_overlaps(
     null chrom or on-value match nothing.
 
     The call is eager whatever the ``output_type`` (``limit`` takes the head of the finished table, ``pyarrow.RecordBatchReader``
-    reads it).  Not offered: ``first`` / ``last`` / ``collapse`` / ``distinct`` / ``median``, string columns, the streaming and
-    Arrow-stream entries, several devices."""
+    reads it).  ``median`` and other quantiles are ``pb.map_quantiles`` / ``pb.map_median``, not an ``agg`` operation.  Not offered:
+    ``first`` / ``last`` / ``collapse`` / ``distinct``, string columns, the streaming and Arrow-stream entries, several devices."""
     mo, f1, f2 = _validate_overlap_thresholds(min_overlap, min_frac1, min_frac2)
     on_cols = _validate_overlap_input(cols1, cols2, on_cols, ("_1", "_2"), output_type)
     _check_on_cols_present(on_cols, df1, df2)
@@ -1669,6 +1669,128 @@ def map_overlaps(
         for out, column in _agg_outputs(name, ops, t2.schema.field(name).type, res).items():
             table = table.append_column(out, column)
     return _finish_eager(table, output_type, zero_based, limit)
+
+
+def _map_quantile_matrix(what, df1, df2, value, qs, method, on_cols, cols1, cols2, output_type, min_overlap, min_frac1, min_frac2, names):
+    """-> (t1, zero_based, values (n, len(qs)) in the engine's dtype or float64, null bool[n], the value column's arrow type);
+    ``names(value)`` = the output column names, checked against df1's before the engine is touched."""
+    mo, f1, f2 = _validate_overlap_thresholds(min_overlap, min_frac1, min_frac2)
+    on_cols = _validate_overlap_input(cols1, cols2, on_cols, ("_1", "_2"), "pyarrow.Table" if output_type == "numpy.ndarray" else output_type)
+    _check_on_cols_present(on_cols, df1, df2)
+    zero_based = validate_coordinate_systems(df1, df2)
+    c2 = list(DEFAULT_INTERVAL_COLUMNS if cols2 is None else cols2)
+    t1, t2, probe, build, n_contigs, _keys = _prepare(df1, df2, cols1, cols2, on_cols)
+    _signal_values(value, t2, c2, on_cols, True)
+    for out in names(value):
+        if out in t1.column_names:
+            raise ValueError(f"{what}: the output column '{out}' of column '{value}' collides with a column of df1")
+    eng = _map_engine(what, "overlap_quantiles")
+    pm, bm = _threshold_minima(probe, build, zero_based, f1, f2)
+    values, valid = _agg_input(t2, value, None)
+    exact = method in ("lower", "higher")
+    if exact:
+        q, upper = qs, [method == "higher"] * len(qs)
+    else:                                                  # lo and hi of each quantile side by side, on float64 values
+        values = values.astype(np.float64)
+        q, upper = [x for x in qs for _ in (0, 1)], [False, True] * len(qs)
+    v, count = eng.overlap_quantiles(probe, build, strict=zero_based, n_contigs=n_contigs, values=values, valid=valid, q=q, upper=upper,
+                                     min_overlap=mo, probe_min=pm, build_min=bm)
+    null = count == 0
+    typ = t2.schema.field(value).type
+    if exact:
+        return t1, zero_based, v, null, typ
+    _lo, _hi, g = quantile_ranks(count[:, None], np.asarray(qs, np.float64)[None, :])
+    vlo, vhi = v[:, 0::2], v[:, 1::2]
+    with np.errstate(invalid="ignore", over="ignore"):
+        val = (vlo + vhi) / 2.0 if method == "midpoint" else vlo + (vhi - vlo) * g
+    val = np.where((vlo == vhi) | (g == 0.0), vlo, val)
+    return t1, zero_based, np.where(null[:, None], np.nan, val), null, typ
+
+
+def map_quantiles(
+    df1,
+    df2,
+    value,
+    q=(0.25, 0.5, 0.75),
+    method: str = "linear",
+    on_cols: Union[list, None] = None,
+    cols1: Union[list, None] = ["chrom", "start", "end"],
+    cols2: Union[list, None] = ["chrom", "start", "end"],
+    output_type: str = "polars.LazyFrame",
+    limit: Union[int, None] = None,
+    *,
+    min_overlap: Union[int, None] = None,
+    min_frac1: Union[float, None] = None,
+    min_frac2: Union[float, None] = None,
+):
+    """Exact quantiles of a df2 value column over the df2 intervals that overlap every df1 interval (``bedtools map -o median``
+    and its quartiles): ``pb.map_quantiles(genes, peaks, "score", q=[0.25, 0.5, 0.75])`` returns the df1 columns plus
+    ``score_q0.25``, ``score_q0.5`` and ``score_q0.75``, one row per df1 row in df1 row order.  Selected on the device: no pair
+    is enumerated, none leaves it, nothing is sorted.
+
+    ``value`` names ONE df2 column (signed integers, unsigned integers up to 32 bits, float32 or float64; not an interval or
+    ``on_cols`` column).  For a df1 row let v[0] <= ... <= v[m - 1] be the non-null values of the df2 rows it matches, sorted;
+    NaN values sort last, as in ``np.sort``.  For a quantile q in [0, 1]: h = q (m - 1) in float64, lo = floor(h), hi = ceil(h),
+    g = h - lo (``quantile_ranks``), and ``method``, with numpy's names, selects ``"lower"`` v[lo] | ``"higher"`` v[hi] (both
+    the column's own type) | ``"midpoint"`` (v[lo] + v[hi]) / 2 | ``"linear"`` (default) v[lo] + (v[hi] - v[lo]) g (both
+    Float64; v[lo] itself where v[lo] == v[hi] or g == 0, so that infinities give no NaN).  For ``"midpoint"`` and ``"linear"``
+    the values are converted to float64 first: the result is exact for integers below 2^53 in magnitude.  The device answers
+    the order statistics; the interpolation is host arithmetic on them.
+
+    Output columns are ``<value>_q<q>`` with q as ``repr(float(q))``, in the given order; ``q``: 1 .. 8 distinct values in
+    [0, 1], else ``ValueError``; a name that is already a df1 column is a ``ValueError``.  df1 rows that match no non-null
+    value get null.  ``output_type="numpy.ndarray"`` returns the bare (n, len(q)) float64 matrix with NaN for null.
+
+    Which df2 rows count, ``on_cols`` and ``min_overlap`` / ``min_frac1`` / ``min_frac2`` (keyword-only) are as in
+    ``map_overlaps``: the number of values under a row is its ``count`` there.  Identities: q = 0 / q = 1 with ``"lower"`` are
+    ``map_overlaps``' ``min`` / ``max`` for columns without NaN.
+
+    The call is eager whatever the ``output_type`` (``limit`` takes the head of the finished table,
+    ``pyarrow.RecordBatchReader`` reads it).  Not offered: quantiles per merged interval (``pb.merge``), a weighted (signal)
+    median, ``first`` / ``last`` / ``collapse`` / ``distinct`` / ``mode``, string columns, the streaming and Arrow-stream entries,
+    several devices (``NotImplementedError``), more than 8 quantiles per call."""
+    qs = _validate_quantiles(q, method)
+    t1, zero_based, val, null, typ = _map_quantile_matrix("map_quantiles", df1, df2, value, qs, method, on_cols, cols1, cols2, output_type,
+                                                          min_overlap, min_frac1, min_frac2, lambda name: [f"{name}_q{x!r}" for x in qs])
+    if output_type == "numpy.ndarray":
+        return np.where(null[:, None], np.nan, val.astype(np.float64))
+    mask = null if null.any() else None
+    for k, x in enumerate(qs):
+        a = np.ascontiguousarray(val[:, k])
+        if method in ("lower", "higher"):
+            column = pc.cast(pa.array(np.where(null, 0, a) if mask is not None else a, mask=mask), typ)
+        else:
+            column = pa.array(a, type=pa.float64(), mask=mask)
+        t1 = t1.append_column(f"{value}_q{x!r}", column)
+    return _finish_eager(t1, output_type, zero_based, limit)
+
+
+def map_median(
+    df1,
+    df2,
+    value,
+    on_cols: Union[list, None] = None,
+    cols1: Union[list, None] = ["chrom", "start", "end"],
+    cols2: Union[list, None] = ["chrom", "start", "end"],
+    output_type: str = "polars.LazyFrame",
+    limit: Union[int, None] = None,
+    *,
+    min_overlap: Union[int, None] = None,
+    min_frac1: Union[float, None] = None,
+    min_frac2: Union[float, None] = None,
+):
+    """The median of a df2 value column over the df2 intervals that overlap every df1 interval, as ``bedtools map -o median``
+    gives it: ``map_quantiles`` with ``q = 0.5`` and ``method="linear"`` -- the middle value of an odd count, the mean of the two
+    middle values of an even one -- as the one Float64 column ``<value>_median``; null where no non-null value matches.  Exact
+    for integers below 2^53 in magnitude.  ``output_type="numpy.ndarray"``: the bare (n, 1) float64 matrix, NaN for null.
+
+    Arguments, what is matched and what is not offered: as ``map_quantiles``."""
+    t1, zero_based, val, null, _typ = _map_quantile_matrix("map_median", df1, df2, value, [0.5], "linear", on_cols, cols1, cols2, output_type,
+                                                           min_overlap, min_frac1, min_frac2, lambda name: [f"{name}_median"])
+    if output_type == "numpy.ndarray":
+        return val
+    t1 = t1.append_column(f"{value}_median", pa.array(np.ascontiguousarray(val[:, 0]), type=pa.float64(), mask=null if null.any() else None))
+    return _finish_eager(t1, output_type, zero_based, limit)
 
 
 _SIGNAL_STATS = ("size", "bases", "sum", "mean0", "mean", "min", "max")
@@ -1732,7 +1854,8 @@ def signal_summary(
     each df1 row and value column.
 
     Eager whatever the ``output_type``; ``limit`` takes the head of the finished table.  Not offered: the streaming and
-    Arrow-stream entries, several devices, ``median`` and other order statistics."""
+    Arrow-stream entries, several devices, a weighted ``median`` and other weighted order statistics (the unweighted ones are
+    ``pb.map_quantiles``)."""
     mo, f1, f2 = _validate_overlap_thresholds(min_overlap, min_frac1, min_frac2)
     on_cols = _validate_overlap_input(cols1, cols2, on_cols, ("_1", "_2"), output_type)
     _check_on_cols_present(on_cols, df1, df2)
