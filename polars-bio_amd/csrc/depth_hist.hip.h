@@ -10,11 +10,10 @@
 //
 // k_depth_hist, the region form.  A workgroup owns P consecutive probes and their P x bins uint64 histograms in LDS,
 // P = floor(IVJ_HIST_LDS_BYTES / (bins * 8)) clamped to [1, IVJ_HIST_MAX_TILE].  The block ranges of the tile are laid out flat
-// (exclusive scan of i1 - i0) and walked in chunks of DH_CH items, one block per lane, on the plan of thresh.hip.h: a 16-bit mark
-// at each probe's first item of the chunk, max-scanned, maps an item to its probe.  Neighbouring lanes hold neighbouring blocks;
+// and walked with the candidate walk of cand_walk.hip.h (walk_offsets, walk_marks, the strided test loop), one block per lane,
+// the "candidates" being the blocks of the exact range.  Neighbouring lanes hold neighbouring blocks;
 // their depths usually differ, so two lanes rarely add to one address (the LDS unit serialises those that do: D = 1 puts every
-// item of a probe on one address and stays correct).  A range may span any number of chunks.  Tile-local offsets are kept
-// modulo 2^32 as in thresh.hip.h.  After the walk bin 0 = |Q| - sum of the other bins, and the tile's P x bins block, contiguous in
+// item of a probe on one address and stays correct).  A range may span any number of chunks.  After the walk bin 0 = |Q| - sum of the other bins, and the tile's P x bins block, contiguous in
 // the row-major output, leaves as 16-byte stores.  No output is read back, no global atomic is used.
 // LDS: the histograms are dynamic; beside them 8 KiB of per-probe {first block, offset, start, end} and 8 KiB shared in turn by
 // the contig metadata (LM, range phase only) and the marks and scan words (walk phase only): 64 KiB + 16 KiB, so that two
@@ -27,25 +26,20 @@
 // Integer adds commute: the table is bit-identical from run to run.  What bounds it: 16 bytes read per block, and at most
 // bins global atomics per tile plus one per block outside the tile's first contig.
 #pragma once
+#include "cand_walk.hip.h"
 #include "depth_query.hip.h"
 
 namespace ivj {
 
-constexpr int DH_THREADS = 256;
-constexpr int DH_ITEMS = 2;                                  // probes per thread
-constexpr int DH_MAXP = DH_THREADS * DH_ITEMS;               // = IVJ_HIST_MAX_TILE
-constexpr int DH_CH = 2048;                                  // items per chunk (one 16-byte mark vector per thread)
+constexpr int DH_THREADS = 256, DH_CH = 2048;             // contig form: threads and blocks per workgroup
 constexpr int DH_MAX_BINS = 1024;                            // = IVJ_MAX_HIST_DEPTH + 1
 constexpr int DH_ROW_PER_THREAD_BINS = 16;                   // up to this many bins a thread sums a row, above a wavefront does
-static_assert(DH_CH * 2 == DH_THREADS * 16, "one uint4 of marks per thread");
-static_assert(DH_MAXP < 65535, "probe index + 1 must fit the 16-bit marks");
-static_assert(DH_THREADS == SCAN_THREADS, "block_exclusive_scan is written for SCAN_THREADS");
 
 // the walk's words, and the contig metadata they share their LDS with
 struct DhWalk {
-    __align__(16) uint16_t marks[DH_CH];
-    int scan_i[DH_THREADS / kWave];
-    long long scan_ll[DH_THREADS / kWave];
+    __align__(16) uint16_t marks[WALK_CH];
+    int scan_i[WALK_WAVES];
+    long long scan_ll[WALK_WAVES];
 };
 constexpr int DH_SCRATCH = 2 * CM_LDS * 16 > (int)sizeof(DhWalk) ? 2 * CM_LDS * 16 : (int)sizeof(DhWalk);
 
@@ -75,13 +69,13 @@ __device__ __forceinline__ void dh_range(const DqIndex& ix, const int4 m0, const
 // size only): every row is |Q| in bin 0.  P probes per workgroup, `dyn` bytes of dynamic LDS >= P * (D + 1) * 8.
 // out: row-major n x (D + 1), 8-byte aligned.
 template <bool STRICT, bool LM>
-__global__ __launch_bounds__(DH_THREADS) void k_depth_hist(DqIndex ix, int have, const int4* __restrict__ brec, const int32_t* __restrict__ pc,
+__global__ __launch_bounds__(WALK_THREADS) void k_depth_hist(DqIndex ix, int have, const int4* __restrict__ brec, const int32_t* __restrict__ pc,
                                                            const int32_t* __restrict__ ps, const int32_t* __restrict__ pe, int64_t n, int P, int D,
                                                            unsigned long long* __restrict__ out) {
     extern __shared__ __align__(16) unsigned long long l_hist[];
-    __shared__ int l_lo[DH_MAXP];                          // first block of the probe
-    __shared__ uint32_t l_off[DH_MAXP];                    // tile-local offset of its first item, modulo 2^32
-    __shared__ int2 l_q[DH_MAXP];                          // {start, end}
+    __shared__ int l_lo[WALK_TILE];                          // first block of the probe
+    __shared__ uint32_t l_off[WALK_TILE];                    // tile-local offset of its first item, modulo 2^32
+    __shared__ int2 l_q[WALK_TILE];                          // {start, end}
     __shared__ __align__(16) unsigned char l_u[DH_SCRATCH];
     const int4* l_cm = reinterpret_cast<const int4*>(l_u);
     DhWalk& W = *reinterpret_cast<DhWalk*>(l_u);
@@ -90,18 +84,17 @@ __global__ __launch_bounds__(DH_THREADS) void k_depth_hist(DqIndex ix, int have,
     const int64_t r0 = (int64_t)blockIdx.x * P;
     const int np = (int)((n - r0) < (int64_t)P ? (n - r0) : (int64_t)P);      // >= 1 by the grid
     const int cnt = np * bins;                                                // <= the LDS budget / 8
-    for (int i = tid; i < cnt; i += DH_THREADS) l_hist[i] = 0ull;
+    for (int i = tid; i < cnt; i += WALK_THREADS) l_hist[i] = 0ull;
     if (LM && have) {
         int4* cm = reinterpret_cast<int4*>(l_u);
-        for (int i = tid; i < 2 * ix.n_contigs; i += DH_THREADS) cm[i] = ix.cmeta_j[i];
+        for (int i = tid; i < 2 * ix.n_contigs; i += WALK_THREADS) cm[i] = ix.cmeta_j[i];
     }
     __syncthreads();
     // the block range and |Q| of every probe
-    int cn[DH_ITEMS];
-    long long tsum = 0;
+    int cn[WALK_ITEMS];
 #pragma unroll
-    for (int k = 0; k < DH_ITEMS; ++k) {
-        const int q = tid * DH_ITEMS + k;
+    for (int k = 0; k < WALK_ITEMS; ++k) {
+        const int q = tid * WALK_ITEMS + k;
         int32_t c = -1, s = 0, e = 0;
         if (q < np) { c = pc[r0 + q]; s = ps[r0 + q]; e = pe[r0 + q]; }
         const bool empty = STRICT ? (s >= e) : (s > e);
@@ -114,77 +107,38 @@ __global__ __launch_bounds__(DH_THREADS) void k_depth_hist(DqIndex ix, int have,
             dh_range<STRICT>(ix, m0, m1, s, e, i0, i1);
         }
         cn[k] = i1 > i0 ? i1 - i0 : 0;
-        tsum += cn[k];
         l_lo[q] = i0; l_q[q] = make_int2(s, e);
         if (ok) l_hist[q * bins] = (unsigned long long)((long long)e - (long long)s + (STRICT ? 0ll : 1ll));
     }
     __syncthreads();                                       // the contig metadata is read: its LDS turns into the walk's words
     long long T;
-    long long off[DH_ITEMS];
-    off[0] = block_exclusive_scan(tsum, SumOp(), 0ll, W.scan_ll, &T);
+    long long off[WALK_ITEMS];
+    walk_offsets(cn, W.scan_ll, off, T);
 #pragma unroll
-    for (int k = 1; k < DH_ITEMS; ++k) off[k] = off[k - 1] + cn[k - 1];
-#pragma unroll
-    for (int k = 0; k < DH_ITEMS; ++k) l_off[tid * DH_ITEMS + k] = (uint32_t)off[k];
-    uint4* marks4 = reinterpret_cast<uint4*>(W.marks);
-    for (long long c0 = 0; c0 < T; c0 += DH_CH) {
-        const int nC = (int)((T - c0) < (long long)DH_CH ? (T - c0) : (long long)DH_CH);
-        __syncthreads();                                   // the previous chunk is done with the marks; l_off is published
-        marks4[tid] = make_uint4(0u, 0u, 0u, 0u);
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < DH_ITEMS; ++k) {
-            if (cn[k] == 0) continue;
-            const long long rel = off[k] - c0;
-            if (rel >= 0 && rel < (long long)nC) W.marks[rel] = (uint16_t)(tid * DH_ITEMS + k + 1);
-            else if (rel < 0 && rel + cn[k] > 0) W.marks[0] = (uint16_t)(tid * DH_ITEMS + k + 1);
-        }
-        __syncthreads();
-        {
-            uint4 v = marks4[tid];
-            uint32_t wd[4] = {v.x, v.y, v.z, v.w};
-            uint32_t tmax = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const uint32_t a = wd[j] & 0xffffu, b = wd[j] >> 16;
-                tmax = tmax > a ? tmax : a;
-                tmax = tmax > b ? tmax : b;
-            }
-            int tot;
-            uint32_t run = (uint32_t)block_exclusive_scan((int)tmax, MaxOp(), 0, W.scan_i, &tot);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const uint32_t a = wd[j] & 0xffffu, b = wd[j] >> 16;
-                run = run > a ? run : a;
-                const uint32_t na = run;
-                run = run > b ? run : b;
-                wd[j] = na | (run << 16);
-            }
-            marks4[tid] = make_uint4(wd[0], wd[1], wd[2], wd[3]);
-        }
-        __syncthreads();
+    for (int k = 0; k < WALK_ITEMS; ++k) l_off[tid * WALK_ITEMS + k] = (uint32_t)off[k];
+    for (long long c0 = 0; c0 < T; c0 += WALK_CH) {
+        const int nC = walk_chunk_len(T, c0);
+        walk_marks(W.marks, W.scan_i, c0, nC, off, cn);   // (its first barrier publishes l_off)
         const uint32_t c0lo = (uint32_t)c0;
-        for (int i = tid; i < nC; i += DH_THREADS) {
-            int q = (int)W.marks[i] - 1;
-            q = q < 0 ? 0 : q;                             // (every item of a chunk lies at or after a mark)
-            const int p = l_lo[q] + (int)(c0lo + (uint32_t)i - l_off[q]);
-            const int2 qq = l_q[q];
-            const int4 r = brec[p];                        // {start, end, depth, 0}
+        for (int i = tid; i < nC; i += WALK_THREADS) {
+            const WalkAt at = walk_probe(l_lo, l_off, W.marks, i, c0lo);
+            const int2 qq = l_q[at.q];
+            const int4 r = brec[at.p];                     // {start, end, depth, 0}
             const long long lo = qq.x > r.x ? qq.x : r.x, hi = qq.y < r.y ? qq.y : r.y;
             const int bin = r.z < 0 ? 0 : (r.z < D ? r.z : D);
-            atomicAdd(&l_hist[q * bins + bin], (unsigned long long)(hi - lo + (STRICT ? 0ll : 1ll)));
+            atomicAdd(&l_hist[at.q * bins + bin], (unsigned long long)(hi - lo + (STRICT ? 0ll : 1ll)));
         }
     }
     __syncthreads();
     // bin 0 holds |Q|: take the row's other bins off it
     if (bins <= DH_ROW_PER_THREAD_BINS) {
-        for (int r = tid; r < np; r += DH_THREADS) {
+        for (int r = tid; r < np; r += WALK_THREADS) {
             unsigned long long sum = 0;
             for (int d = 1; d <= D; ++d) sum += l_hist[r * bins + d];
             l_hist[r * bins] -= sum;
         }
     } else {
-        for (int r = w; r < np; r += DH_THREADS / kWave) {
+        for (int r = w; r < np; r += WALK_WAVES) {
             unsigned long long sum = 0;
             for (int d = 1 + lane; d <= D; d += kWave) sum += l_hist[r * bins + d];
 #pragma unroll
@@ -198,7 +152,7 @@ __global__ __launch_bounds__(DH_THREADS) void k_depth_hist(DqIndex ix, int have,
     const int head = (int)((reinterpret_cast<uintptr_t>(o) >> 3) & 1u);       // <= cnt: cnt >= 2
     const int npairs = (cnt - head) >> 1;
     typedef unsigned long long v2u __attribute__((ext_vector_type(2)));
-    for (int i = tid; i < npairs; i += DH_THREADS) {
+    for (int i = tid; i < npairs; i += WALK_THREADS) {
         v2u v; v.x = l_hist[head + 2 * i]; v.y = l_hist[head + 2 * i + 1];
         __builtin_nontemporal_store(v, reinterpret_cast<v2u*>(o + head + 2 * i));
     }

@@ -5,10 +5,9 @@
 // are in the list at depth 0).  For K ranks per row:  out[row][j] = v[rank[row][j]];  -1 for a rank outside [0, L) and for a row
 // without a position or outside the dictionary.  Quantiles are the host's arithmetic on ranks (range_op.quantile_ranks).
 //
-// k_depth_quant keeps k_depth_hist's plan up to the add (depth_hist.hip.h): the exact block range [i0, i1) of each probe from
-// dh_range, the tile's ranges laid flat by an exclusive scan, the walk in chunks of DH_CH items with one 16-byte {start, end,
-// depth, 0} record per lane, the max-scanned 16-bit marks that map an item to its probe, the two edge clips.  A range may span any
-// number of chunks.  What differs is what an item does and that the walk is repeated: a radix select, most significant digit
+// k_depth_quant walks as k_depth_hist does (depth_hist.hip.h): the exact block range [i0, i1) of each probe from dh_range, then
+// the candidate walk of cand_walk.hip.h with the strided test loop, one 16-byte {start, end, depth, 0} record per lane, and the
+// two edge clips.  A range may span any number of chunks.  What differs is what an item does and that the walk is repeated: a radix select, most significant digit
 // first, B = IVJ_QUANT_BITS bits per pass, over the depths under every row.
 //
 // State per (row, rank), in LDS: a 2^B-bin uint64 histogram (dynamic), a 32-bit prefix (the digits chosen so far) and the residual
@@ -46,14 +45,14 @@ constexpr int DQT_NB = 1 << DQT_BITS;                                        // 
 constexpr int DQT_MAXPK = IVJ_QUANT_LDS_BYTES / (DQT_NB * 8);                // (row, rank) states of a workgroup
 constexpr uint32_t DQT_NONE = 0xffffffffu, DQT_ZERO = 0xfffffffeu;           // settled: the answer is -1 / 0
 static_assert(DQT_BITS >= 4 && DQT_BITS <= 8, "below 4 bits P x K exceeds the tile; above 8 a row of 16 ranks exceeds the budget");
-static_assert(DQT_MAXPK <= DH_MAXP && IVJ_QUANT_MAX_TILE == DH_MAXP, "a thread holds DH_ITEMS probes of the tile");
+static_assert(DQT_MAXPK <= WALK_TILE && IVJ_QUANT_MAX_TILE == WALK_TILE, "a thread holds WALK_ITEMS probes of the tile");
 static_assert(IVJ_MAX_QUANT_RANKS * DQT_NB * 8 <= IVJ_QUANT_LDS_BYTES, "one row's histograms fit the budget");
 
 // the walk's words and the select state, and the contig metadata they share their LDS with
 struct DqtWords {
-    __align__(16) uint16_t marks[DH_CH];
-    int scan_i[DH_THREADS / kWave];
-    long long scan_ll[DH_THREADS / kWave];
+    __align__(16) uint16_t marks[WALK_CH];
+    int scan_i[WALK_WAVES];
+    long long scan_ll[WALK_WAVES];
     uint32_t tmax;                                         // the tile's maximum depth
     uint32_t pad[3];
     uint32_t prefix[DQT_MAXPK];
@@ -62,59 +61,22 @@ struct DqtWords {
 constexpr int DQT_SCRATCH = 2 * CM_LDS * 16 > (int)sizeof(DqtWords) ? 2 * CM_LDS * 16 : (int)sizeof(DqtWords);
 static_assert(DQT_SCRATCH % 16 == 0, "the dynamic LDS starts on a 16-byte boundary");
 
-// One walk over the tile's T items, DH_CH per chunk, on k_depth_hist's plan: f(q, len, depth) for every (probe of the tile, block
-// under it) with the block clipped to the probe.  cn / off: the thread's DH_ITEMS probes' item counts and tile-local offsets;
+// One walk over the tile's T items (cand_walk.hip.h, the strided test loop): f(q, len, depth) for every (probe of the tile, block
+// under it) with the block clipped to the probe.  cn / off: the thread's WALK_ITEMS probes' item counts and tile-local offsets;
 // l_base[q] = first block - offset modulo 2^32.  Uniform: every thread of the workgroup calls it.
 template <bool STRICT, class F>
-__device__ __forceinline__ void dqt_walk(const long long T, const int (&cn)[DH_ITEMS], const long long (&off)[DH_ITEMS], DqtWords& W,
+__device__ __forceinline__ void dqt_walk(const long long T, const int (&cn)[WALK_ITEMS], const long long (&off)[WALK_ITEMS], DqtWords& W,
                                          const uint32_t* l_base, const int2* l_q, const int4* __restrict__ brec, F&& f) {
-    const int tid = threadIdx.x;
-    uint4* marks4 = reinterpret_cast<uint4*>(W.marks);
-    for (long long c0 = 0; c0 < T; c0 += DH_CH) {
-        const int nC = (int)((T - c0) < (long long)DH_CH ? (T - c0) : (long long)DH_CH);
-        __syncthreads();                                   // the previous chunk is done with the marks
-        marks4[tid] = make_uint4(0u, 0u, 0u, 0u);
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < DH_ITEMS; ++k) {
-            if (cn[k] == 0) continue;
-            const long long rel = off[k] - c0;
-            if (rel >= 0 && rel < (long long)nC) W.marks[rel] = (uint16_t)(tid * DH_ITEMS + k + 1);
-            else if (rel < 0 && rel + cn[k] > 0) W.marks[0] = (uint16_t)(tid * DH_ITEMS + k + 1);
-        }
-        __syncthreads();
-        {
-            uint4 v = marks4[tid];
-            uint32_t wd[4] = {v.x, v.y, v.z, v.w};
-            uint32_t tmax = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const uint32_t a = wd[j] & 0xffffu, b = wd[j] >> 16;
-                tmax = tmax > a ? tmax : a;
-                tmax = tmax > b ? tmax : b;
-            }
-            int tot;
-            uint32_t run = (uint32_t)block_exclusive_scan((int)tmax, MaxOp(), 0, W.scan_i, &tot);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const uint32_t a = wd[j] & 0xffffu, b = wd[j] >> 16;
-                run = run > a ? run : a;
-                const uint32_t na = run;
-                run = run > b ? run : b;
-                wd[j] = na | (run << 16);
-            }
-            marks4[tid] = make_uint4(wd[0], wd[1], wd[2], wd[3]);
-        }
-        __syncthreads();
+    for (long long c0 = 0; c0 < T; c0 += WALK_CH) {
+        const int nC = walk_chunk_len(T, c0);
+        walk_marks(W.marks, W.scan_i, c0, nC, off, cn);
         const uint32_t c0lo = (uint32_t)c0;
-        for (int i = tid; i < nC; i += DH_THREADS) {
-            int q = (int)W.marks[i] - 1;
-            q = q < 0 ? 0 : q;                             // (every item of a chunk lies at or after a mark)
-            const int p = (int)(l_base[q] + c0lo + (uint32_t)i);
-            const int2 qq = l_q[q];
-            const int4 r = brec[p];                        // {start, end, depth, 0}
+        for (int i = threadIdx.x; i < nC; i += WALK_THREADS) {
+            const WalkAt at = walk_probe(l_base, W.marks, i, c0lo);
+            const int2 qq = l_q[at.q];
+            const int4 r = brec[at.p];                     // {start, end, depth, 0}
             const long long lo = qq.x > r.x ? qq.x : r.x, hi = qq.y < r.y ? qq.y : r.y;
-            if (r.z > 0) f(q, (unsigned long long)(hi - lo + (STRICT ? 0ll : 1ll)), (uint32_t)r.z);
+            if (r.z > 0) f(at.q, (unsigned long long)(hi - lo + (STRICT ? 0ll : 1ll)), (uint32_t)r.z);
         }
     }
 }
@@ -123,12 +85,12 @@ __device__ __forceinline__ void dqt_walk(const long long T, const int (&cn)[DH_I
 // size only).  P probes per workgroup, K ranks per probe, `dyn` bytes of dynamic LDS >= P * K * DQT_NB * 8.
 // ranks: row-major n x K, 0-based; out: row-major n x K.
 template <bool STRICT, bool LM>
-__global__ __launch_bounds__(DH_THREADS) void k_depth_quant(DqIndex ix, int have, const int4* __restrict__ brec, const int32_t* __restrict__ pc,
+__global__ __launch_bounds__(WALK_THREADS) void k_depth_quant(DqIndex ix, int have, const int4* __restrict__ brec, const int32_t* __restrict__ pc,
                                                             const int32_t* __restrict__ ps, const int32_t* __restrict__ pe, int64_t n, int P, int K,
                                                             const int64_t* __restrict__ ranks, int32_t* __restrict__ out) {
     extern __shared__ __align__(16) unsigned long long l_hist[];
-    __shared__ uint32_t l_base[DH_MAXP];                   // first block of the probe - tile-local offset of its first item, modulo 2^32
-    __shared__ int2 l_q[DH_MAXP];                          // {start, end}; {0, -1} for a probe without a position or outside the dictionary
+    __shared__ uint32_t l_base[WALK_TILE];                   // first block of the probe - tile-local offset of its first item, modulo 2^32
+    __shared__ int2 l_q[WALK_TILE];                          // {start, end}; {0, -1} for a probe without a position or outside the dictionary
     __shared__ __align__(16) unsigned char l_u[DQT_SCRATCH];
     const int4* l_cm = reinterpret_cast<const int4*>(l_u);
     DqtWords& W = *reinterpret_cast<DqtWords*>(l_u);
@@ -137,19 +99,18 @@ __global__ __launch_bounds__(DH_THREADS) void k_depth_quant(DqIndex ix, int have
     const int np = (int)((n - r0) < (int64_t)P ? (n - r0) : (int64_t)P);      // >= 1 by the grid
     const int cnt = np * K;                                                   // <= DQT_MAXPK
     unsigned long long* l_cov = l_hist;                    // the survey's covered positions per probe, before the first pass
-    for (int i = tid; i < np; i += DH_THREADS) l_cov[i] = 0ull;
+    for (int i = tid; i < np; i += WALK_THREADS) l_cov[i] = 0ull;
     if (LM && have) {
         int4* cm = reinterpret_cast<int4*>(l_u);
-        for (int i = tid; i < 2 * ix.n_contigs; i += DH_THREADS) cm[i] = ix.cmeta_j[i];
+        for (int i = tid; i < 2 * ix.n_contigs; i += WALK_THREADS) cm[i] = ix.cmeta_j[i];
     }
     __syncthreads();
     // the block range of every probe
-    int cn[DH_ITEMS];
-    int lo0[DH_ITEMS];
-    long long tsum = 0;
+    int cn[WALK_ITEMS];
+    int lo0[WALK_ITEMS];
 #pragma unroll
-    for (int k = 0; k < DH_ITEMS; ++k) {
-        const int q = tid * DH_ITEMS + k;
+    for (int k = 0; k < WALK_ITEMS; ++k) {
+        const int q = tid * WALK_ITEMS + k;
         int32_t c = -1, s = 0, e = 0;
         if (q < np) { c = pc[r0 + q]; s = ps[r0 + q]; e = pe[r0 + q]; }
         const bool empty = STRICT ? (s >= e) : (s > e);
@@ -163,17 +124,14 @@ __global__ __launch_bounds__(DH_THREADS) void k_depth_quant(DqIndex ix, int have
         }
         cn[k] = i1 > i0 ? i1 - i0 : 0;
         lo0[k] = i0;
-        tsum += cn[k];
         l_q[q] = ok ? make_int2(s, e) : make_int2(0, -1);
     }
     __syncthreads();                                       // the contig metadata is read: its LDS turns into the walk's words
     long long T;
-    long long off[DH_ITEMS];
-    off[0] = block_exclusive_scan(tsum, SumOp(), 0ll, W.scan_ll, &T);
+    long long off[WALK_ITEMS];
+    walk_offsets(cn, W.scan_ll, off, T);
 #pragma unroll
-    for (int k = 1; k < DH_ITEMS; ++k) off[k] = off[k - 1] + cn[k - 1];
-#pragma unroll
-    for (int k = 0; k < DH_ITEMS; ++k) l_base[tid * DH_ITEMS + k] = (uint32_t)lo0[k] - (uint32_t)off[k];
+    for (int k = 0; k < WALK_ITEMS; ++k) l_base[tid * WALK_ITEMS + k] = (uint32_t)lo0[k] - (uint32_t)off[k];
     if (tid == 0) W.tmax = 0u;                             // (the walk's first barrier publishes it and l_base)
     // survey: covered positions per probe, the tile's maximum depth
     {
@@ -191,7 +149,7 @@ __global__ __launch_bounds__(DH_THREADS) void k_depth_quant(DqIndex ix, int have
     }
     __syncthreads();
     // the state of every (probe, rank): settled (-1, or 0 among the uncovered positions), or the rank among the covered ones
-    for (int i = tid; i < cnt; i += DH_THREADS) {
+    for (int i = tid; i < cnt; i += WALK_THREADS) {
         const int q = i / K;
         const int2 qq = l_q[q];
         const long long L = (long long)qq.y - (long long)qq.x + (STRICT ? 0ll : 1ll);
@@ -209,7 +167,7 @@ __global__ __launch_bounds__(DH_THREADS) void k_depth_quant(DqIndex ix, int have
     for (int p = npass - 1; p >= 0; --p) {
         const int shift = p * DQT_BITS;
         __syncthreads();                                   // covered[] and the previous pass's bins are read
-        for (int i = tid; i < cnt * DQT_NB; i += DH_THREADS) l_hist[i] = 0ull;
+        for (int i = tid; i < cnt * DQT_NB; i += WALK_THREADS) l_hist[i] = 0ull;
         // (the walk's first barrier publishes the zeros and the state)
         dqt_walk<STRICT>(T, cn, off, W, l_base, l_q, brec, [&](int q, unsigned long long len, uint32_t d) {
             const uint32_t hi = (uint32_t)((unsigned long long)d >> (shift + DQT_BITS));
@@ -218,7 +176,7 @@ __global__ __launch_bounds__(DH_THREADS) void k_depth_quant(DqIndex ix, int have
                 if (W.prefix[q * K + j] == hi) atomicAdd(&l_hist[(q * K + j) * DQT_NB + bin], len);
         });
         __syncthreads();
-        for (int i = tid; i < cnt; i += DH_THREADS) {
+        for (int i = tid; i < cnt; i += WALK_THREADS) {
             const uint32_t pf = W.prefix[i];
             if (pf & 0x80000000u) continue;                // settled
             const unsigned long long rs = W.res[i];
@@ -235,7 +193,7 @@ __global__ __launch_bounds__(DH_THREADS) void k_depth_quant(DqIndex ix, int have
     }
     __syncthreads();
     int32_t* o = out + r0 * K;
-    for (int i = tid; i < cnt; i += DH_THREADS) {
+    for (int i = tid; i < cnt; i += WALK_THREADS) {
         const uint32_t pf = W.prefix[i];
         o[i] = pf == DQT_ZERO ? 0 : (int32_t)pf;           // DQT_NONE is -1
     }

@@ -13,7 +13,7 @@
 namespace {
 
 static_assert(DH_MAX_BINS == IVJ_MAX_HIST_DEPTH + 1, "the contig form's LDS histogram holds IVJ_MAX_HIST_DEPTH + 1 bins");
-static_assert(DH_MAXP == IVJ_HIST_MAX_TILE, "a thread holds DH_ITEMS probes of the tile");
+static_assert(WALK_TILE == IVJ_HIST_MAX_TILE, "a thread holds WALK_ITEMS probes of the tile");
 
 // argument checks shared by all four entries, whatever the number of rows
 int depth_hist_check(int32_t max_depth, const void* hist) {
@@ -87,7 +87,7 @@ int depth_hist_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe, const ivj
     const int64_t tiles = (n + P - 1) / P;
     const int rc = with_bool(strict, nb > 0 && v.n_contigs <= CM_LDS, [&](auto S, auto LM) -> int {
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_depth_hist<S, LM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        LAUNCH_LDS(ctx, "depth_hist", (k_depth_hist<S, LM>), tiles, DH_THREADS, lds, v, (int)(nb > 0), (const int4*)rec, probe->contig, probe->start, probe->end,
+        LAUNCH_LDS(ctx, "depth_hist", (k_depth_hist<S, LM>), tiles, WALK_THREADS, lds, v, (int)(nb > 0), (const int4*)rec, probe->contig, probe->start, probe->end,
                    n, P, (int)D, (unsigned long long*)hist);
         return IVJ_OK;
     });

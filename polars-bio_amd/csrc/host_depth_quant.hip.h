@@ -35,7 +35,7 @@ int depth_quant_dev(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe, const iv
     const int64_t tiles = (n + P - 1) / P;
     const int rc = with_bool(strict, B.nb > 0 && B.v.n_contigs <= CM_LDS, [&](auto S, auto LM) -> int {
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_depth_quant<S, LM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        LAUNCH_LDS(ctx, "depth_quant", (k_depth_quant<S, LM>), tiles, DH_THREADS, lds, B.v, (int)(B.nb > 0), (const int4*)B.rec, probe->contig, probe->start,
+        LAUNCH_LDS(ctx, "depth_quant", (k_depth_quant<S, LM>), tiles, WALK_THREADS, lds, B.v, (int)(B.nb > 0), (const int4*)B.rec, probe->contig, probe->start,
                    probe->end, n, P, (int)K, ranks, out);
         return IVJ_OK;
     });

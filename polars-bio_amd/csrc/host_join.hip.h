@@ -232,13 +232,13 @@ int overlap_fused(ivj_ctx* ctx, ivj_index* ix, const ivj_side* probe, const ivj_
         qc = ctx->pt_c; qs = ctx->pt_s; qe = ctx->pt_e; ids = ctx->pt_row;
     }
     for (int attempt = 0; attempt < 2; ++attempt) {
-        const int64_t tiles = flat ? (n + FLAT_TILE - 1) / FLAT_TILE : (n + PROBE_TILE - 1) / PROBE_TILE;
+        const int64_t tiles = flat ? (n + WALK_TILE - 1) / WALK_TILE : (n + PROBE_TILE - 1) / PROBE_TILE;
         HIP_TRY(hipMemsetAsync(state, 0, 24, ctx->stream));
         const bool vec = aligned16(qc) && aligned16(qs) && aligned16(qe);
         IndexView v = view_of(ix);
         with_bool(opts->filter_op == IVJ_FILTER_STRICT, [&](auto S) {
             if (flat) {
-                LAUNCH(ctx, "overlap_flat", (k_overlap_flat<S>), 8 * ((tiles + 7) / 8), FLAT_THREADS, v, qc, qs, qe, ids, n, vec, (long long)capacity, state, out_p, out_b, (int)rank_counts);
+                LAUNCH(ctx, "overlap_flat", (k_overlap_flat<S>), 8 * ((tiles + 7) / 8), WALK_THREADS, v, qc, qs, qe, ids, n, vec, (long long)capacity, state, out_p, out_b, (int)rank_counts);
             } else {
                 LAUNCH(ctx, "overlap_fused", (k_overlap_fused<S>), 8 * ((tiles + 7) / 8), PROBE_THREADS, v, qc, qs, qe, ids, n, vec, (long long)capacity, state, out_p, out_b);
             }

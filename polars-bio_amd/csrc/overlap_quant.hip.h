@@ -8,11 +8,10 @@
 // sign bit flipped; doubles with every NaN made the canonical quiet NaN first, then u ^ (sign ? ~0 : 1 << 63) -- np.sort's order,
 // NaN last, with -0.0 placed just below +0.0 (they compare equal, so which zero a rank returns is unspecified).
 //
-// The walk (ovq_walk) restates oagg_chunk's geometry: the loose candidate range of every probe of the tile from flat_range, never
-// tightened, the ranges laid flat by an exclusive scan and walked in chunks of THRESH_CH with one candidate per lane, the
-// max-scanned 16-bit marks that map a candidate to its probe, the plain or (THRESH) the thresholded predicate on the 16-byte rec4
-// record, then the validity byte and the 8 value bytes of the same sorted position (k_oagg_gather's arrays).  A range may span any
-// number of chunks.  What differs is what a match does, and that the walk is repeated.
+// The walk (ovq_walk) is the candidate walk of cand_walk.hip.h with the strided test loop: the loose candidate range of every probe
+// of the tile from flat_range, never tightened, then per candidate the plain or (THRESH) the thresholded predicate on the 16-byte
+// rec4 record (cand_match), the validity byte and the 8 value bytes of the same sorted position (k_oagg_gather's arrays).  A range
+// may span any number of chunks.  What differs from overlap_agg.hip.h is what a match does, and that the walk is repeated.
 //
 // State per (row, rank), in LDS: a 2^B-bin uint32 histogram (dynamic; B = IVJ_OVQ_BITS), the 64-bit prefix (the key bits settled so
 // far) and the 32-bit residual rank among the values whose key starts with that prefix (m < 2^31).  A workgroup owns
@@ -41,7 +40,6 @@ constexpr int OVQ_BITS = IVJ_OVQ_BITS;
 constexpr int OVQ_NB = 1 << OVQ_BITS;                                        // bins per (row, rank)
 constexpr int OVQ_NDIG = (64 + OVQ_BITS - 1) / OVQ_BITS;                     // digits of a key (the top one may be short)
 constexpr int OVQ_MAXPK = IVJ_OVQ_LDS_BYTES / (OVQ_NB * 4);                  // (row, rank) states of a workgroup
-constexpr int OVQ_WAVES = THRESH_THREADS / kWave;
 static_assert(OVQ_BITS >= 4 && OVQ_BITS <= 8, "below 4 bits P x K exceeds the tile; above 8 a row of 16 ranks exceeds the budget");
 static_assert(IVJ_OVQ_MAX_TILE == THRESH_TILE, "a thread holds THRESH_ITEMS probes of the tile");
 static_assert(IVJ_MAX_OVQ_RANKS * OVQ_NB * 4 <= IVJ_OVQ_LDS_BYTES, "one row's histograms fit the budget");
@@ -74,76 +72,31 @@ struct OvqLds {
     uint32_t thr[THRESH_TILE];        // max(min_overlap, probe_min[row])
     uint32_t m[THRESH_TILE];          // matching valid candidates of the probe
     __align__(16) uint16_t marks[THRESH_CH];
-    int scan_i[OVQ_WAVES];
-    long long scan_ll[OVQ_WAVES];
-    unsigned long long kand[OVQ_WAVES], kor[OVQ_WAVES];
+    int scan_i[WALK_WAVES];
+    long long scan_ll[WALK_WAVES];
+    unsigned long long kand[WALK_WAVES], kor[WALK_WAVES];
     double rq[IVJ_MAX_OVQ_RANKS];
     uint32_t rup[IVJ_MAX_OVQ_RANKS];
     unsigned long long prefix[OVQ_MAXPK];
     uint32_t res[OVQ_MAXPK];
 };
 
-// One walk over the tile's T candidates, THRESH_CH per chunk: f(q, key) for every (probe q of the tile, candidate) that matches and
-// whose value is valid.  cn / off: the thread's THRESH_ITEMS probes' candidate counts and tile-local offsets.  Uniform: every
-// thread of the workgroup calls it.
+// One walk over the tile's T candidates (cand_walk.hip.h, the strided test loop): f(q, key) for every (probe q of the tile,
+// candidate) that matches and whose value is valid.  cn / off: the thread's THRESH_ITEMS probes' candidate counts and tile-local
+// offsets.  Uniform: every thread of the workgroup calls it.
 template <bool STRICT, bool THRESH, int DTYPE, class F>
 __device__ __forceinline__ void ovq_walk(const IndexView& ix, const uint32_t* __restrict__ bm_sorted, const unsigned long long* __restrict__ vals_sorted,
                                          const uint8_t* __restrict__ ok_sorted, const long long T, const int (&cn)[THRESH_ITEMS],
                                          const long long (&off)[THRESH_ITEMS], OvqLds& L, F&& f) {
-    const int tid = threadIdx.x;
-    uint4* marks4 = reinterpret_cast<uint4*>(L.marks);
     for (long long c0 = 0; c0 < T; c0 += THRESH_CH) {
-        const int nC = (int)((T - c0) < (long long)THRESH_CH ? (T - c0) : (long long)THRESH_CH);
-        __syncthreads();                                   // the previous chunk is done with the marks
-        marks4[tid] = make_uint4(0u, 0u, 0u, 0u);
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < THRESH_ITEMS; ++k) {
-            if (cn[k] == 0) continue;
-            const long long rel = off[k] - c0;
-            if (rel >= 0 && rel < (long long)nC) L.marks[rel] = (uint16_t)(tid * THRESH_ITEMS + k + 1);
-            else if (rel < 0 && rel + cn[k] > 0) L.marks[0] = (uint16_t)(tid * THRESH_ITEMS + k + 1);
-        }
-        __syncthreads();
-        {
-            uint4 v = marks4[tid];
-            uint32_t wd[4] = {v.x, v.y, v.z, v.w};
-            uint32_t tmax = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const uint32_t a = wd[j] & 0xffffu, b = wd[j] >> 16;
-                tmax = tmax > a ? tmax : a;
-                tmax = tmax > b ? tmax : b;
-            }
-            int tot;
-            uint32_t run = (uint32_t)block_exclusive_scan((int)tmax, MaxOp(), 0, L.scan_i, &tot);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const uint32_t a = wd[j] & 0xffffu, b = wd[j] >> 16;
-                run = run > a ? run : a;
-                const uint32_t na = run;
-                run = run > b ? run : b;
-                wd[j] = na | (run << 16);
-            }
-            marks4[tid] = make_uint4(wd[0], wd[1], wd[2], wd[3]);
-        }
-        __syncthreads();
+        const int nC = walk_chunk_len(T, c0);
+        walk_marks(L.marks, L.scan_i, c0, nC, off, cn);
         const uint32_t c0lo = (uint32_t)c0;
-        for (int i = tid; i < nC; i += THRESH_THREADS) {
-            int q = (int)L.marks[i] - 1;
-            q = q < 0 ? 0 : q;                             // (every candidate of a chunk lies at or after a mark)
-            const int p = (int)(L.base[q] + c0lo + (uint32_t)i);
-            const int2 qq = L.q[q];
-            const int4 v = ix.rec4[p];                     // {start, end, build row, -}
-            bool m;
-            if (THRESH) {
-                uint32_t thr = L.thr[q];
-                if (bm_sorted) { const uint32_t bm = bm_sorted[p]; thr = thr > bm ? thr : bm; }
-                m = thresh_match<STRICT>(qq.x, qq.y, v.x, v.y, thr);
-            } else {
-                m = lt_op<STRICT>(v.x, qq.y) && lt_op<STRICT>(qq.x, v.y);
-            }
-            if (m && ok_sorted[p] != 0) f(q, ovq_key<DTYPE>(vals_sorted[p]));
+        for (int i = threadIdx.x; i < nC; i += THRESH_THREADS) {
+            const WalkAt at = walk_probe(L.base, L.marks, i, c0lo);
+            const int4 v = ix.rec4[at.p];                  // {start, end, build row, -}
+            const bool m = cand_match<STRICT, THRESH>(L.q[at.q], v, L.thr[at.q], bm_sorted, at.p);
+            if (m && ok_sorted[at.p] != 0) f(at.q, ovq_key<DTYPE>(vals_sorted[at.p]));
         }
     }
 }
@@ -173,7 +126,6 @@ __global__ __launch_bounds__(THRESH_THREADS, 2) void k_overlap_quant(IndexView i
         if (tid == j) { L.rq[j] = rq.q[j]; L.rup[j] = rq.upper[j]; }
     // the loose candidate range of every probe
     int cn[THRESH_ITEMS], lo[THRESH_ITEMS];
-    long long tsum = 0;
 #pragma unroll
     for (int k = 0; k < THRESH_ITEMS; ++k) {
         const int q = tid * THRESH_ITEMS + k;
@@ -189,14 +141,11 @@ __global__ __launch_bounds__(THRESH_THREADS, 2) void k_overlap_quant(IndexView i
         // (THRESH) a probe that covers no position, or whose own minimum is "never", has no candidates
         const bool can = THRESH ? (valid && thr != THRESH_NEVER && (STRICT ? s < e : s <= e)) : valid;
         flat_range<STRICT>(ix, c, s, e, can, lo[k], cn[k]);
-        tsum += cn[k];
         L.q[q] = make_int2(s, e); L.thr[q] = thr; L.m[q] = 0u;
     }
     long long T;
     long long off[THRESH_ITEMS];
-    off[0] = block_exclusive_scan(tsum, SumOp(), 0ll, L.scan_ll, &T);
-#pragma unroll
-    for (int k = 1; k < THRESH_ITEMS; ++k) off[k] = off[k - 1] + cn[k - 1];
+    walk_offsets(cn, L.scan_ll, off, T);
 #pragma unroll
     for (int k = 0; k < THRESH_ITEMS; ++k) L.base[tid * THRESH_ITEMS + k] = (uint32_t)lo[k] - (uint32_t)off[k];
     // survey: matches per probe, the AND and OR of the tile's keys  (the walk's first barrier publishes the LDS arrays)
@@ -214,7 +163,7 @@ __global__ __launch_bounds__(THRESH_THREADS, 2) void k_overlap_quant(IndexView i
     __syncthreads();                                       // ... and m[] is complete
     ka = ~0ull; ko = 0ull;
 #pragma unroll
-    for (int k = 0; k < OVQ_WAVES; ++k) { ka &= L.kand[k]; ko |= L.kor[k]; }
+    for (int k = 0; k < WALK_WAVES; ++k) { ka &= L.kand[k]; ko |= L.kor[k]; }
     const unsigned long long vary = (ka & ~ko) ? 0ull : (ka ^ ko);            // no match in the tile: AND = ~0 and OR = 0, no pass
     // the state of every (probe, request): the rank among the probe's m values; the digits that do not vary are the AND's
     for (int i = tid; i < cnt; i += THRESH_THREADS) {

@@ -12,15 +12,13 @@
 // LOOSE candidate range [lo', hi') that flat_range reads from tab2 with two table reads (flat.hip.h; the tables of build_flat,
 // read-only).  The range is that of the UNSHRUNK probe: it is NOT tightened by the minima (a probe shrunk by m > len / 2 inverts,
 // and the range of the plain probe is a superset whatever the minima are).  The only candidates left out are those of probes that
-// cannot match at all: rows that cover no position and rows whose own minimum is "never".  The candidates of a tile of probes are
-// laid out flat (exclusive scan of the range lengths) and every lane tests one candidate on its 16-byte rec4 record plus -- when
-// build minima were given -- the 4-byte minimum of the same sorted position (build_min permuted into index order once per call by
+// cannot match at all: rows that cover no position and rows whose own minimum is "never".  Every lane tests one candidate on its
+// 16-byte rec4 record plus -- when build minima were given -- the 4-byte minimum of the same sorted position (build_min permuted into index order once per call by
 // k_thresh_gather: nothing is gathered by row per candidate).
 //
-// Ranges of any length: a tile walks its flat candidate space in chunks of THRESH_CH; a probe's range may span any number of
-// chunks (a contig-wide build row keeps the range of every probe of the contig open down to that row: there is no second path to
-// fall back to, the chunks simply go on).  Tile-local candidate offsets are kept modulo 2^32 in LDS: the index of a candidate
-// inside its probe's range (< 2^30 build rows) is exact under that arithmetic however many candidates the tile has.
+// Ranges of any length: the tile's candidates are walked as cand_walk.hip.h describes, with the sub-range test loop; a probe's range
+// may span any number of chunks (a contig-wide build row keeps the range of every probe of the contig open down to that row:
+// there is no second path to fall back to, the chunks simply go on).
 //
 // Two forms of one kernel:
 //   count (EMIT = false)  per-tile totals (the exclusive scan of which places the tiles' output ranges) and, when asked, per-probe
@@ -35,14 +33,14 @@
 
 namespace ivj {
 
+// The geometry of this kernel and of those built on ThreshLds (overlap_agg, overlap_quant, signal) under the family's own names,
+// by value: the tests size their cases by them.  It is the shared walk's, which holds the asserts on it.
 constexpr int THRESH_THREADS = 256;
 constexpr int THRESH_ITEMS = 2;
 constexpr int THRESH_TILE = THRESH_THREADS * THRESH_ITEMS;   // probes per workgroup
-constexpr int THRESH_CH = 2048;                              // candidates per chunk (one 16-byte mark vector per thread)
+constexpr int THRESH_CH = 2048;                              // candidates per chunk
 constexpr uint32_t THRESH_NEVER = 0xffffffffu;
-static_assert(THRESH_CH * 2 == THRESH_THREADS * 16, "one uint4 of marks per thread");
-static_assert(THRESH_TILE < 65535, "probe index + 1 must fit the 16-bit marks");
-static_assert(THRESH_THREADS == SCAN_THREADS, "block_exclusive_scan is written for SCAN_THREADS");
+static_assert(THRESH_THREADS == WALK_THREADS && THRESH_ITEMS == WALK_ITEMS && THRESH_CH == WALK_CH, "the geometry of cand_walk.hip.h");
 
 // m_sorted[p] = m[b_row[p]]: the build-side minima in index order
 __global__ void k_thresh_gather(const int32_t* __restrict__ b_row, const uint32_t* __restrict__ m, int64_t n_index, int64_t n_rows,
@@ -62,6 +60,19 @@ __device__ __forceinline__ bool thresh_match(int32_t as, int32_t ae, int32_t bs,
     return thr != THRESH_NEVER && ov >= need;
 }
 
+// a probe's minimum raised to the build row's (bm_sorted NULL: no build minima), and the predicate of a candidate-test kernel
+// with and without thresholds: the plain form is b.start (<) q.end && q.start (<) b.end as written.  qq = the probe's {start, end},
+// v = the candidate's rec4 record at sorted position p.
+__device__ __forceinline__ uint32_t cand_thr(uint32_t thr, const uint32_t* __restrict__ bm_sorted, int p) {
+    if (bm_sorted) { const uint32_t bm = bm_sorted[p]; thr = thr > bm ? thr : bm; }
+    return thr;
+}
+template <bool STRICT, bool THRESH>
+__device__ __forceinline__ bool cand_match(const int2 qq, const int4 v, uint32_t thr, const uint32_t* __restrict__ bm_sorted, int p) {
+    if (THRESH) return thresh_match<STRICT>(qq.x, qq.y, v.x, v.y, cand_thr(thr, bm_sorted, p));
+    return lt_op<STRICT>(v.x, qq.y) && lt_op<STRICT>(qq.x, v.y);
+}
+
 struct ThreshLds {
     int lo[THRESH_TILE];              // first candidate position of the probe
     uint32_t off[THRESH_TILE];        // tile-local offset of its first candidate, modulo 2^32
@@ -71,95 +82,38 @@ struct ThreshLds {
     int32_t row[THRESH_TILE];         // emit form: the row id to report
     __align__(16) uint16_t marks[THRESH_CH];
     int32_t st_b[THRESH_CH];
-    int scan_i[THRESH_THREADS / kWave];
-    long long scan_ll[THRESH_THREADS / kWave];
-    long long wtot[THRESH_THREADS / kWave];
+    int scan_i[WALK_WAVES];
+    long long scan_ll[WALK_WAVES];
+    long long wtot[WALK_WAVES];
 };
 
-// One chunk of nC <= THRESH_CH candidates starting at tile-local candidate offset c0.  Builds the candidate -> probe map (marks:
-// probe index + 1 at the probe's first candidate of the chunk, max-scanned), then wavefront w tests the candidates
-// [w * per, (w + 1) * per).  EMIT: the matches of a wavefront are staged at st_b / marks[w * per + rank] (marks recycled as the probe
-// index of the staged pair: rank <= index, and the lanes of a step have read their marks before any of them writes).  COUNTS: the
-// matches of one probe inside a step are consecutive lanes; the first of them adds their number to the probe's LDS counter.
-// Returns the number of matches of this wavefront.
+// One chunk of nC <= THRESH_CH candidates starting at tile-local candidate offset c0: the candidate -> probe map (walk_marks), then
+// wavefront w tests the candidates of its sub-range (walk_sub).  EMIT: the matches of a wavefront are staged at st_b / marks[wb + rank]
+// for walk_emit_chunk.  COUNTS: per-probe counts into L.cnt (walk_count_heads).  Returns the number of matches of this wavefront.
 template <bool STRICT, bool EMIT, bool COUNTS>
 __device__ __forceinline__ int thresh_chunk(const IndexView& ix, const uint32_t* __restrict__ bm_sorted, long long c0, int nC,
                                             const long long (&off)[THRESH_ITEMS], const int (&cn)[THRESH_ITEMS], ThreshLds& L) {
-    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
+    const int lane = threadIdx.x & (kWave - 1);
     const unsigned long long lt_lanes = (1ull << lane) - 1ull;
-    const int per = ((nC + THRESH_THREADS - 1) / THRESH_THREADS) * kWave;
-    uint4* marks4 = reinterpret_cast<uint4*>(L.marks);
-    __syncthreads();                                       // the previous chunk is done with marks / st_b
-    marks4[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < THRESH_ITEMS; ++k) {
-        if (cn[k] == 0) continue;
-        const long long rel = off[k] - c0;
-        if (rel >= 0 && rel < (long long)nC) L.marks[rel] = (uint16_t)(threadIdx.x * THRESH_ITEMS + k + 1);
-        else if (rel < 0 && rel + cn[k] > 0) L.marks[0] = (uint16_t)(threadIdx.x * THRESH_ITEMS + k + 1);
-    }
-    __syncthreads();
-    {
-        uint4 v = marks4[threadIdx.x];
-        uint32_t wd[4] = {v.x, v.y, v.z, v.w};
-        uint32_t tmax = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint32_t a = wd[j] & 0xffffu, b = wd[j] >> 16;
-            tmax = tmax > a ? tmax : a;
-            tmax = tmax > b ? tmax : b;
-        }
-        int tot;
-        uint32_t run = (uint32_t)block_exclusive_scan((int)tmax, MaxOp(), 0, L.scan_i, &tot);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint32_t a = wd[j] & 0xffffu, b = wd[j] >> 16;
-            run = run > a ? run : a;
-            const uint32_t na = run;
-            run = run > b ? run : b;
-            wd[j] = na | (run << 16);
-        }
-        marks4[threadIdx.x] = make_uint4(wd[0], wd[1], wd[2], wd[3]);
-    }
-    __syncthreads();
-    const int wb = w * per;
-    const int we = (wb + per) < nC ? (wb + per) : nC;
+    walk_marks(L.marks, L.scan_i, c0, nC, off, cn);
+    const WalkSub sub = walk_sub(nC);
     const uint32_t c0lo = (uint32_t)c0;
     int cnt = 0;
-    for (int i0 = wb; i0 < we; i0 += kWave) {
+    for (int i0 = sub.wb; i0 < sub.we; i0 += kWave) {
         const int i = i0 + lane;
-        const bool valid = i < we;
-        int q = valid ? (int)L.marks[i] - 1 : 0;
-        q = q < 0 ? 0 : q;                                 // (every candidate of a chunk lies at or after a mark)
-        const int lo = L.lo[q];
-        const uint32_t of = L.off[q];
-        const int2 qq = L.q[q];
-        uint32_t thr = L.thr[q];
-        const int p = lo + (int)(c0lo + (uint32_t)i - of);
+        const bool valid = i < sub.we;
+        const WalkAt at = walk_probe(L.lo, L.off, L.marks, i, c0lo, valid);
+        const int2 qq = L.q[at.q];
+        const uint32_t thr = L.thr[at.q];
         int4 v = make_int4(0, 0, 0, 0);                    // {start, end, build row, -}
-        if (valid) {
-            v = ix.rec4[p];
-            if (bm_sorted) { const uint32_t bm = bm_sorted[p]; thr = thr > bm ? thr : bm; }
-        }
-        const bool m = valid && thresh_match<STRICT>(qq.x, qq.y, v.x, v.y, thr);
+        if (valid) v = ix.rec4[at.p];
+        const bool m = valid && cand_match<STRICT, true>(qq, v, thr, bm_sorted, at.p);
         const unsigned long long mm = __ballot(m);
-        if (COUNTS && mm != 0ull) {                        // uniform
-            const int qseg = valid ? q : -1;
-            const int qprev = __shfl_up(qseg, 1, kWave);
-            const bool head = lane == 0 || qprev != qseg;
-            const unsigned long long hb = __ballot(head);
-            if (head && valid) {
-                const unsigned long long above = hb & ~((2ull << lane) - 1ull);   // the heads after this one
-                const unsigned long long upto = above ? ((above & (0ull - above)) - 1ull) : ~0ull;
-                const int c = (int)__popcll(mm & upto & ~lt_lanes);
-                if (c) atomicAdd(&L.cnt[q], (uint32_t)c);
-            }
-        }
+        if (COUNTS) walk_count_heads(L.cnt, at.q, valid, mm);
         if (EMIT && m) {
-            const int r = wb + cnt + (int)__popcll(mm & lt_lanes);
+            const int r = sub.wb + cnt + (int)__popcll(mm & lt_lanes);
             L.st_b[r] = v.z;
-            L.marks[r] = (uint16_t)q;
+            L.marks[r] = (uint16_t)at.q;
         }
         cnt += (int)__popcll(mm);
     }
@@ -185,16 +139,8 @@ __global__ __launch_bounds__(THRESH_THREADS, 4) void k_overlap_thresh(IndexView 
     if (tile >= ntiles) return;                            // uniform
     const int64_t i0 = (int64_t)tile * THRESH_TILE + (int64_t)threadIdx.x * THRESH_ITEMS;
     int32_t c[THRESH_ITEMS], s[THRESH_ITEMS], e[THRESH_ITEMS], at[THRESH_ITEMS];
-    load_items_nt(pc, i0, n, vec_ok, -1, c);
-    load_items_nt(ps, i0, n, vec_ok, 0, s);
-    load_items_nt(pe, i0, n, vec_ok, 0, e);
-    if (pos) load_items(pos, i0, n, vec_ok, 0, at);
-    else {
-#pragma unroll
-        for (int k = 0; k < THRESH_ITEMS; ++k) at[k] = (int32_t)(i0 + k);
-    }
+    load_probe_items(pc, ps, pe, pos, i0, n, vec_ok, c, s, e, at);
     int lo[THRESH_ITEMS], cn[THRESH_ITEMS];
-    long long tsum = 0;
 #pragma unroll
     for (int k = 0; k < THRESH_ITEMS; ++k) {
         const bool valid = i0 + k < n;
@@ -203,7 +149,6 @@ __global__ __launch_bounds__(THRESH_THREADS, 4) void k_overlap_thresh(IndexView 
         // a probe that covers no position, or whose own minimum is "never", has no candidates
         const bool can = valid && thr != THRESH_NEVER && (STRICT ? s[k] < e[k] : s[k] <= e[k]);
         flat_range<STRICT>(ix, c[k], s[k], e[k], can, lo[k], cn[k]);
-        tsum += cn[k];
         const int q = threadIdx.x * THRESH_ITEMS + k;
         L.lo[q] = lo[k]; L.q[q] = make_int2(s[k], e[k]); L.thr[q] = thr;
         if (!EMIT) L.cnt[q] = 0u;
@@ -211,35 +156,26 @@ __global__ __launch_bounds__(THRESH_THREADS, 4) void k_overlap_thresh(IndexView 
     }
     long long T;
     long long off[THRESH_ITEMS];
-    off[0] = block_exclusive_scan(tsum, SumOp(), 0ll, L.scan_ll, &T);
-#pragma unroll
-    for (int k = 1; k < THRESH_ITEMS; ++k) off[k] = off[k - 1] + cn[k - 1];
+    walk_offsets(cn, L.scan_ll, off, T);
 #pragma unroll
     for (int k = 0; k < THRESH_ITEMS; ++k) L.off[threadIdx.x * THRESH_ITEMS + k] = (uint32_t)off[k];
-    // (the first barrier inside thresh_chunk publishes the LDS arrays)
+    // (the first barrier of walk_marks publishes the LDS arrays)
     if (EMIT) {
         if (T == 0) return;                                // uniform
         long long running = tile_tot[tile];
         for (long long c0 = 0; c0 < T; c0 += THRESH_CH) {
-            const int nC = (int)((T - c0) < (long long)THRESH_CH ? (T - c0) : (long long)THRESH_CH);
+            const int nC = walk_chunk_len(T, c0);
             const int cnt = thresh_chunk<STRICT, true, false>(ix, bm_sorted, c0, nC, off, cn, L);
-            if (lane == 0) L.wtot[w] = cnt;                // (readers of the previous values have passed a barrier inside thresh_chunk)
-            __syncthreads();
-            long long cpre = 0, ctot = 0;
-#pragma unroll
-            for (int k = 0; k < THRESH_THREADS / kWave; ++k) { const long long x = L.wtot[k]; if (k < w) cpre += x; ctot += x; }
-            const int wb = w * (((nC + THRESH_THREADS - 1) / THRESH_THREADS) * kWave);
-            for (int j = lane; j < cnt; j += kWave) {
-                __builtin_nontemporal_store(L.row[L.marks[wb + j]], out_probe + running + cpre + j);
-                __builtin_nontemporal_store(L.st_b[wb + j], out_build + running + cpre + j);
-            }
-            running += ctot;
+            running += walk_emit_chunk(L.wtot, cnt, nC, [&](int slot, long long o) {
+                __builtin_nontemporal_store(L.row[L.marks[slot]], out_probe + running + o);
+                __builtin_nontemporal_store(L.st_b[slot], out_build + running + o);
+            });
         }
         return;
     }
     long long wcnt = 0;                                    // matches of this wavefront over the whole tile
     for (long long c0 = 0; c0 < T; c0 += THRESH_CH) {
-        const int nC = (int)((T - c0) < (long long)THRESH_CH ? (T - c0) : (long long)THRESH_CH);
+        const int nC = walk_chunk_len(T, c0);
         if (counts) wcnt += thresh_chunk<STRICT, false, true>(ix, bm_sorted, c0, nC, off, cn, L);
         else wcnt += thresh_chunk<STRICT, false, false>(ix, bm_sorted, c0, nC, off, cn, L);
     }
@@ -248,7 +184,7 @@ __global__ __launch_bounds__(THRESH_THREADS, 4) void k_overlap_thresh(IndexView 
     if (tile_tot && threadIdx.x == 0) {
         long long tot = 0;
 #pragma unroll
-        for (int k = 0; k < THRESH_THREADS / kWave; ++k) tot += L.wtot[k];
+        for (int k = 0; k < WALK_WAVES; ++k) tot += L.wtot[k];
         tile_tot[tile] = tot;
     }
     if (counts) {

@@ -1,6 +1,6 @@
 // window.hip.h -- pb.window / pb.count_window: every build (df2) row within a distance of every probe (df1) row, with the distance
 // (bedtools window -w / -l / -r / -sw, pyranges join(slack=), bioframe pair_by_distance).  A candidate-test join on the plan of
-// thresh.hip.h; the tables of build_flat (flat.hip.h) are read-only here.
+// thresh.hip.h (the walk of cand_walk.hip.h); the tables of build_flat (flat.hip.h) are read-only here.
 //
 // For a probe row a and a build row b of one contig, everything in 64 bits ((<) is < for 0-based half-open frames, STRICT, and <=
 // for 1-based closed ones, WEAK):
@@ -25,10 +25,9 @@
 // INT32_MIN; a half-open row with start = INT32_MAX or end = INT32_MIN has start >= end, covers no position and never pairs.
 // The range is NOT narrowed by min_distance.  Probes that cover no position have no candidates.
 //
-// THE WALK is that of k_overlap_thresh: 512 probes per workgroup, their ranges laid flat by an exclusive scan, chunks of 2048
-// candidates with the mark / max-scan candidate -> probe map, one lane per candidate on its 16-byte rec4 record.  Ranges of any
-// length: the chunks simply go on (a contig-wide build row keeps every range of its contig open); no hand-over to another kernel.
-// Tile-local candidate offsets are kept modulo 2^32 in LDS (exact inside one probe's range of < 2^30 rows).
+// THE WALK is that of cand_walk.hip.h with the sub-range test loop, as in k_overlap_thresh: WIN_TILE probes per workgroup, one lane
+// per candidate on its 16-byte rec4 record.  Ranges of any length: the chunks simply go on (a contig-wide build row keeps every
+// range of its contig open); no hand-over to another kernel.
 //
 // Forms of one kernel (FORM):
 //   WIN_COUNT  per-tile totals (their exclusive scan places the tiles' output ranges) and, when asked, per-probe int64 counts
@@ -48,15 +47,15 @@
 
 namespace ivj {
 
+// The kernel's geometry under its own names, by value (the tests size their cases by them): the shared walk's.
 constexpr int WIN_THREADS = 256;
 constexpr int WIN_ITEMS = 2;
 constexpr int WIN_TILE = WIN_THREADS * WIN_ITEMS;         // probes per workgroup
-constexpr int WIN_CH = 2048;                              // candidates per chunk (one 16-byte mark vector per thread)
+constexpr int WIN_CH = 2048;                              // candidates per chunk
+static_assert(WIN_THREADS == WALK_THREADS && WIN_ITEMS == WALK_ITEMS && WIN_CH == WALK_CH, "the geometry of cand_walk.hip.h");
 constexpr int WIN_COUNT = 0, WIN_PAIRS = 1, WIN_DIST = 2;
 constexpr uint32_t WIN_SIGN = 0x8000u;                    // staged mark: the build row lies before the probe
-static_assert(WIN_CH * 2 == WIN_THREADS * 16, "one uint4 of marks per thread");
 static_assert(WIN_TILE < (int)WIN_SIGN, "probe index + 1 must leave bit 15 of the 16-bit marks free");
-static_assert(WIN_THREADS == SCAN_THREADS, "block_exclusive_scan is written for SCAN_THREADS");
 
 // the extended probe of the header comment, clamped to int32
 template <bool STRICT>
@@ -93,95 +92,43 @@ struct WindowLds {
     __align__(16) uint16_t marks[WIN_CH];
     int32_t st_b[WIN_CH];
     uint32_t st_d[FORM == WIN_DIST ? WIN_CH : 1];
-    int scan_i[WIN_THREADS / kWave];
-    long long scan_ll[WIN_THREADS / kWave];
-    long long wtot[WIN_THREADS / kWave];
+    int scan_i[WALK_WAVES];
+    long long scan_ll[WALK_WAVES];
+    long long wtot[WALK_WAVES];
 };
 static_assert(sizeof(WindowLds<WIN_DIST>) * 4 <= 160 * 1024, "four resident workgroups per CU");
 
-// One chunk of nC <= WIN_CH candidates starting at tile-local candidate offset c0 (thresh_chunk with the distance predicate).  Emit
-// forms: the matches of a wavefront are staged at st_b / st_d / marks[w * per + rank]; marks is recycled as the probe index of the
-// staged pair, bit 15 = the sign of its distance (rank <= index, and the lanes of a step have read their marks before any of them
-// writes).  COUNTS: the matches of one probe inside a step are consecutive lanes; the first of them adds their number to the probe's
-// LDS counter.  Returns the number of matches of this wavefront.
+// One chunk of nC <= WIN_CH candidates starting at tile-local candidate offset c0: the candidate -> probe map (walk_marks), then
+// wavefront w tests the candidates of its sub-range (walk_sub) with the distance predicate.  Emit forms: the matches of a wavefront
+// are staged at st_b / st_d / marks[wb + rank] for walk_emit_chunk; bit 15 of the staged mark = the sign of the distance.  COUNTS:
+// per-probe counts into L.cr (walk_count_heads).  Returns the number of matches of this wavefront.
 template <bool STRICT, int FORM, bool COUNTS>
 __device__ __forceinline__ int window_chunk(const IndexView& ix, uint32_t min_distance, long long c0, int nC,
                                             const long long (&off)[WIN_ITEMS], const int (&cn)[WIN_ITEMS], WindowLds<FORM>& L) {
-    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
+    const int lane = threadIdx.x & (kWave - 1);
     const unsigned long long lt_lanes = (1ull << lane) - 1ull;
-    const int per = ((nC + WIN_THREADS - 1) / WIN_THREADS) * kWave;
-    uint4* marks4 = reinterpret_cast<uint4*>(L.marks);
-    __syncthreads();                                       // the previous chunk is done with marks / st_b / st_d
-    marks4[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < WIN_ITEMS; ++k) {
-        if (cn[k] == 0) continue;
-        const long long rel = off[k] - c0;
-        if (rel >= 0 && rel < (long long)nC) L.marks[rel] = (uint16_t)(threadIdx.x * WIN_ITEMS + k + 1);
-        else if (rel < 0 && rel + cn[k] > 0) L.marks[0] = (uint16_t)(threadIdx.x * WIN_ITEMS + k + 1);
-    }
-    __syncthreads();
-    {
-        uint4 v = marks4[threadIdx.x];
-        uint32_t wd[4] = {v.x, v.y, v.z, v.w};
-        uint32_t tmax = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint32_t a = wd[j] & 0xffffu, b = wd[j] >> 16;
-            tmax = tmax > a ? tmax : a;
-            tmax = tmax > b ? tmax : b;
-        }
-        int tot;
-        uint32_t run = (uint32_t)block_exclusive_scan((int)tmax, MaxOp(), 0, L.scan_i, &tot);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint32_t a = wd[j] & 0xffffu, b = wd[j] >> 16;
-            run = run > a ? run : a;
-            const uint32_t na = run;
-            run = run > b ? run : b;
-            wd[j] = na | (run << 16);
-        }
-        marks4[threadIdx.x] = make_uint4(wd[0], wd[1], wd[2], wd[3]);
-    }
-    __syncthreads();
-    const int wb = w * per;
-    const int we = (wb + per) < nC ? (wb + per) : nC;      // wb + per <= WIN_CH: every staged index stays inside the chunk arrays
+    walk_marks(L.marks, L.scan_i, c0, nC, off, cn);
+    const WalkSub sub = walk_sub(nC);
     const uint32_t c0lo = (uint32_t)c0;
     int cnt = 0;
-    for (int i0 = wb; i0 < we; i0 += kWave) {
+    for (int i0 = sub.wb; i0 < sub.we; i0 += kWave) {
         const int i = i0 + lane;
-        const bool valid = i < we;
-        int q = valid ? (int)L.marks[i] - 1 : 0;
-        q = q < 0 ? 0 : q;                                 // (every candidate of a chunk lies at or after a mark)
-        const int lo = L.lo[q];
-        const uint32_t of = L.off[q];
-        const int2 qq = L.q[q];
-        const uint32_t el = L.left[q], er = L.right[q];
-        const int p = lo + (int)(c0lo + (uint32_t)i - of);
+        const bool valid = i < sub.we;
+        const WalkAt at = walk_probe(L.lo, L.off, L.marks, i, c0lo, valid);
+        const int2 qq = L.q[at.q];
+        const uint32_t el = L.left[at.q], er = L.right[at.q];
         int4 v = make_int4(0, 0, 0, 0);                    // {start, end, build row, -}
-        if (valid) v = ix.rec4[p];
+        if (valid) v = ix.rec4[at.p];
         uint32_t mag = 0;
         bool before = false;
         const bool m = valid && window_match<STRICT>(qq.x, qq.y, v.x, v.y, el, er, min_distance, mag, before);
         const unsigned long long mm = __ballot(m);
-        if (COUNTS && mm != 0ull) {                        // uniform
-            const int qseg = valid ? q : -1;
-            const int qprev = __shfl_up(qseg, 1, kWave);
-            const bool head = lane == 0 || qprev != qseg;
-            const unsigned long long hb = __ballot(head);
-            if (head && valid) {
-                const unsigned long long above = hb & ~((2ull << lane) - 1ull);   // the heads after this one
-                const unsigned long long upto = above ? ((above & (0ull - above)) - 1ull) : ~0ull;
-                const int c = (int)__popcll(mm & upto & ~lt_lanes);
-                if (c) atomicAdd(&L.cr[q], (uint32_t)c);
-            }
-        }
+        if (COUNTS) walk_count_heads(L.cr, at.q, valid, mm);
         if (FORM != WIN_COUNT && m) {
-            const int r = wb + cnt + (int)__popcll(mm & lt_lanes);
+            const int r = sub.wb + cnt + (int)__popcll(mm & lt_lanes);
             L.st_b[r] = v.z;
             if (FORM == WIN_DIST) L.st_d[r] = mag;
-            L.marks[r] = (uint16_t)((uint32_t)q | (before ? WIN_SIGN : 0u));
+            L.marks[r] = (uint16_t)((uint32_t)at.q | (before ? WIN_SIGN : 0u));
         }
         cnt += (int)__popcll(mm);
     }
@@ -209,16 +156,8 @@ __global__ __launch_bounds__(WIN_THREADS, 4) void k_window(IndexView ix, const i
     if (tile >= ntiles) return;                            // uniform
     const int64_t i0 = (int64_t)tile * WIN_TILE + (int64_t)threadIdx.x * WIN_ITEMS;
     int32_t c[WIN_ITEMS], s[WIN_ITEMS], e[WIN_ITEMS], at[WIN_ITEMS];
-    load_items_nt(pc, i0, n, vec_ok, -1, c);
-    load_items_nt(ps, i0, n, vec_ok, 0, s);
-    load_items_nt(pe, i0, n, vec_ok, 0, e);
-    if (pos) load_items(pos, i0, n, vec_ok, 0, at);
-    else {
-#pragma unroll
-        for (int k = 0; k < WIN_ITEMS; ++k) at[k] = (int32_t)(i0 + k);
-    }
+    load_probe_items(pc, ps, pe, pos, i0, n, vec_ok, c, s, e, at);
     int lo[WIN_ITEMS], cn[WIN_ITEMS];
-    long long tsum = 0;
 #pragma unroll
     for (int k = 0; k < WIN_ITEMS; ++k) {
         const bool valid = i0 + k < n;
@@ -230,7 +169,6 @@ __global__ __launch_bounds__(WIN_THREADS, 4) void k_window(IndexView ix, const i
         int32_t qs, qe;
         window_probe<STRICT>(s[k], e[k], el, er, qs, qe);
         flat_range<STRICT>(ix, c[k], qs, qe, can, lo[k], cn[k]);
-        tsum += cn[k];
         const int q = threadIdx.x * WIN_ITEMS + k;
         L.lo[q] = lo[k]; L.q[q] = make_int2(s[k], e[k]); L.left[q] = el; L.right[q] = er;
         if (FORM == WIN_COUNT) L.cr[q] = 0u;
@@ -238,40 +176,31 @@ __global__ __launch_bounds__(WIN_THREADS, 4) void k_window(IndexView ix, const i
     }
     long long T;
     long long off[WIN_ITEMS];
-    off[0] = block_exclusive_scan(tsum, SumOp(), 0ll, L.scan_ll, &T);
-#pragma unroll
-    for (int k = 1; k < WIN_ITEMS; ++k) off[k] = off[k - 1] + cn[k - 1];
+    walk_offsets(cn, L.scan_ll, off, T);
 #pragma unroll
     for (int k = 0; k < WIN_ITEMS; ++k) L.off[threadIdx.x * WIN_ITEMS + k] = (uint32_t)off[k];
-    // (the first barrier inside window_chunk publishes the LDS arrays)
+    // (the first barrier of walk_marks publishes the LDS arrays)
     if constexpr (FORM != WIN_COUNT) {
         if (T == 0) return;                                // uniform
         long long running = tile_tot[tile];
         for (long long c0 = 0; c0 < T; c0 += WIN_CH) {
-            const int nC = (int)((T - c0) < (long long)WIN_CH ? (T - c0) : (long long)WIN_CH);
+            const int nC = walk_chunk_len(T, c0);
             const int cnt = window_chunk<STRICT, FORM, false>(ix, min_distance, c0, nC, off, cn, L);
-            if (lane == 0) L.wtot[w] = cnt;                // (readers of the previous values have passed a barrier inside window_chunk)
-            __syncthreads();
-            long long cpre = 0, ctot = 0;
-#pragma unroll
-            for (int k = 0; k < WIN_THREADS / kWave; ++k) { const long long x = L.wtot[k]; if (k < w) cpre += x; ctot += x; }
-            const int wb = w * (((nC + WIN_THREADS - 1) / WIN_THREADS) * kWave);
-            for (int j = lane; j < cnt; j += kWave) {
-                const uint32_t mk = L.marks[wb + j];
-                __builtin_nontemporal_store((int32_t)L.cr[mk & (WIN_SIGN - 1u)], out_probe + running + cpre + j);
-                __builtin_nontemporal_store(L.st_b[wb + j], out_build + running + cpre + j);
+            running += walk_emit_chunk(L.wtot, cnt, nC, [&](int slot, long long o) {
+                const uint32_t mk = L.marks[slot];
+                __builtin_nontemporal_store((int32_t)L.cr[mk & (WIN_SIGN - 1u)], out_probe + running + o);
+                __builtin_nontemporal_store(L.st_b[slot], out_build + running + o);
                 if constexpr (FORM == WIN_DIST) {
-                    const long long d = (long long)L.st_d[wb + j];
-                    __builtin_nontemporal_store((mk & WIN_SIGN) ? -d : d, out_dist + running + cpre + j);
+                    const long long d = (long long)L.st_d[slot];
+                    __builtin_nontemporal_store((mk & WIN_SIGN) ? -d : d, out_dist + running + o);
                 }
-            }
-            running += ctot;
+            });
         }
         return;
     } else {
         long long wcnt = 0;                                // matches of this wavefront over the whole tile
         for (long long c0 = 0; c0 < T; c0 += WIN_CH) {
-            const int nC = (int)((T - c0) < (long long)WIN_CH ? (T - c0) : (long long)WIN_CH);
+            const int nC = walk_chunk_len(T, c0);
             if (counts) wcnt += window_chunk<STRICT, WIN_COUNT, true>(ix, min_distance, c0, nC, off, cn, L);
             else wcnt += window_chunk<STRICT, WIN_COUNT, false>(ix, min_distance, c0, nC, off, cn, L);
         }
@@ -280,7 +209,7 @@ __global__ __launch_bounds__(WIN_THREADS, 4) void k_window(IndexView ix, const i
         if (tile_tot && threadIdx.x == 0) {
             long long tot = 0;
 #pragma unroll
-            for (int k = 0; k < WIN_THREADS / kWave; ++k) tot += L.wtot[k];
+            for (int k = 0; k < WALK_WAVES; ++k) tot += L.wtot[k];
             tile_tot[tile] = tot;
         }
         if (counts) {

@@ -500,6 +500,41 @@ def test_limit_rows_in_the_flat_kernel(strict):
 
 
 @gpu
+@pytest.mark.parametrize("degenerate", [pytest.param(False, id="rank_count"), pytest.param(True, id="sweep_count")])
+def test_flat_kernel_tile_of_many_chunks(degenerate):
+    """k_overlap_flat (partition_mode 5) on one tile of 200 probes over 3000 build rows stacked on one position range: about 3000
+    candidates per probe (below FLAT_MAX_CAND), i.e. some 290 chunks of which the last is partial, and every probe's range begins in
+    one chunk and ends in a later one.  The tile's total comes from the two-rank formula, or -- with a probe that covers no position
+    in the tile -- from the counting sweep over the chunks; the pairs are then emitted chunk by chunk.  Compared exactly with the
+    oracle's brute force of the plain predicate."""
+    i = np.arange(3000)
+    build = (np.zeros(3000, np.int32), (1000 + i % 7).astype(np.int32), (2000 - i % 5).astype(np.int32))
+    j = np.arange(200)
+    probe = (np.zeros(200, np.int32), (1000 + j).astype(np.int32), (1500 + 2 * j).astype(np.int32))
+    if degenerate:
+        probe[2][77] = probe[1][77]                        # start == end: the formula is not exact for it, the brute force still pairs it
+    ep, eb = O.overlap_brute(O.Side(*probe), O.Side(*build), True)
+    o = np.lexsort((eb, ep))
+    ep, eb = ep[o], eb[o]
+    assert 199 * 3000 <= len(ep) <= 200 * 3000
+    e = _engine.Engine(0)
+    try:
+        e.enable_timing(2)
+        hp, hb = _fused_overlap(e, probe, build, True, 1, 5, len(ep))
+        t = e.timings()
+        assert "overlap_flat" in t and "overlap_fused" not in t, sorted(t)
+        # the pairs of one probe are contiguous and ordered by (build.start, build row)
+        assert len(np.unique(hp)) == int((hp[1:] != hp[:-1]).sum()) + 1
+        inside = hp[1:] == hp[:-1]
+        ks, kb = build[1][hb].astype(np.int64), hb.astype(np.int64)
+        assert (((ks[1:] > ks[:-1]) | ((ks[1:] == ks[:-1]) & (kb[1:] > kb[:-1]))) | ~inside).all()
+        o = np.lexsort((hb, hp))
+        assert (hp[o] == ep).all() and (hb[o] == eb).all(), "flat kernel, many chunks"
+    finally:
+        e.close()
+
+
+@gpu
 @pytest.mark.parametrize("strict", [True, False])
 def test_limit_rows_in_the_256_bucket_window_kernels(strict):
     probe, build = _big(*BASE)
